@@ -2,18 +2,22 @@
 """Headline benchmark: NUNet-TLS-LSTM frame step, frames/s (one frame = one 256-bin magnitude
 vector of one stream = one 256-sample hop of the 512-pt / 50 % STFT).
 
-    python bench.py                       # 1 GPU, 200 steps, 32 warm-up
+    python bench.py                       # 1 GPU, 200 steps, 32 warm-up: the headline line only
+    python bench.py --full                # + roofline / in-kernel timeline, CPU baseline, parity vs the oracle, other_configs
+    python bench.py --dump-outputs DIR    # + DIR/<name>.npy: what the last timed step computed (float32)
     python bench.py --gpus N              # spawns N ranks itself (torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # what the driver does
 
 Workload (BASELINE.json configs[1]): NUNet-TLS-LSTM, the reference's trained weights, B = 256
 independent streams per GPU, synthetic magnitudes 0.25*|N(0,1)| (default_rng(1234 + first stream of the rank)),
-zero-initialised state, inputs resident in HBM before the timed region.  A "step" is one pass
+zero-initialised state (reset after the clock conditioning, so that the W warm-up + K timed steps start from it and the
+outputs of the last step are the same from run to run), inputs resident in HBM before the timed region.  A "step" is one pass
 of the hot path over the batch (256 frames per GPU).  N > 1 shards the N*256 streams over ranks (weak
 scaling, no data-path collective; RCCL only reduces the timing / frame counters).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, conditions the clocks, warms up, times the steps, writes its outputs
+(--dump-outputs) and prints that line; everything else it can measure or check runs only with --full.
 """
 from __future__ import annotations
 
@@ -55,6 +59,28 @@ PKG = os.path.join(ROOT, "nested-u-net-based-real-time-speech-enhancement-mobile
 def synthetic_pool(batch, n, seed):
     rng = np.random.default_rng(seed)
     return (0.25 * np.abs(rng.standard_normal((n, batch, 256)))).astype(np.float32)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (<name>_rank<r>.npy with several ranks), at most 64 MB in DIR over all
+    ranks; an output larger than its share is reduced to a fixed, seeded sample of its rows (the array as [-1, last axis]), whose
+    indices go to DIR/<name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32) for k, v in arrays.items()}
+    budget = DUMP_BUDGET_BYTES // max(1, world)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        tag = name if world == 1 else "%s_rank%d" % (name, rank)
+        if total > budget:
+            a = a.reshape(-1, a.shape[-1])
+            keep = max(1, int(a.shape[0] * budget // total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(dirname, tag + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, tag + ".npy"), a)
 
 
 def kernel_source_sha16(mode, variant="lstm", streams=1):
@@ -200,6 +226,8 @@ def bench_offline(args, rank, world, local_rank):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert bool(torch.isfinite(out).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"enhanced_mag": outs[0] if batched else torch.stack(outs)}, rank, world)
     if rank == 0:
         # roofline of the block as a whole: the mode is many kernels (one per layer and chunk + 13 scans); its arithmetic is the step's
         # (147.9 MFLOP per frame), executed as three bf16 MFMAs per fp32 product -- priced against the fp32-MFMA peak (the
@@ -214,7 +242,7 @@ def bench_offline(args, rank, world, local_rank):
                             "hbm_layer_fused_gbps": round(fps * 4_151_808 / 1e9, 1),
                             "scan_floor": "13 scans x T x 0.153 us per step = %.2f ms per block of %d frames (serial per stage; chunks overlap them)" % (13 * T_ * 0.153e-3, T_)}
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             b1 = _time_oracle(1, min(8, os.cpu_count() or 1), 6.0)      # one utterance on the CPU = the oracle frame by frame
             cpu = {"value": round(b1[0], 1), "unit": "frames/s", "cores": min(8, os.cpu_count() or 1), "kind": "port",
                    "sample": "oracle/nutls_ref.py, one stream frame by frame: %d frames in %.1f s" % (b1[1], b1[2])}
@@ -382,11 +410,18 @@ def main():
     ap.add_argument("--ctfa-mode", default="frame", choices=["frame", "causal32"],
                     help="causal32: the offline model's 32-frame causal CTFA in the streaming kernel (per-stream attention history kept by the library: "
                          "BASELINE configs[4]'s 'persistent CTFA state'); default: what the reference's streaming graph computes (TA / 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the `other_configs` records of the default line (configs[2], [3]-size, [4])")
-    ap.add_argument("--profile-json", default="", help="write the per-op timeline here")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the unconditioned window, roofline and in-kernel "
+                         "timeline (kernel_report), the CPU baseline, parity against the oracle and the `other_configs` records")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the `other_configs` records of the default line (configs[2], [3]-size, [4])")
+    ap.add_argument("--profile-json", default="", help="--full: write the per-op timeline here")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.profile_json and not args.full:
+        ap.error("--profile-json needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -477,9 +512,9 @@ def main():
     # metric is a steady-state rate, so the device is brought to steady clocks with the same step before the W warm-up steps; the timed
     # region below is still exactly --steps steps behind exactly --warmup warm-up steps.
     # ... and the same W + K steps are timed once BEFORE the conditioning (`value_unconditioned`: what the driver's arguments measure on a GPU
-    # that was idle), so that every line shows what the conditioning is worth on its box
+    # that was idle), so that every --full line shows what the conditioning is worth on its box
     uncond = None
-    if args.condition_ms > 0 and not selftest and world == 1:
+    if args.full and args.condition_ms > 0 and not selftest and world == 1:
         for s in range(args.warmup):
             one_step(s)
         sync()
@@ -496,15 +531,20 @@ def main():
                 one_step(s)
             cond_steps += 16
             sync()
+    if not selftest and (uncond is not None or cond_steps):
+        eng.reset()          # the W + K steps below start from the zero state, whatever the untimed steps above did
     for s in range(args.warmup):
         one_step(s)
     barrier()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        one_step(s)
+        last = one_step(s)
     sync()
     elapsed = time.perf_counter() - t0
     barrier()
+    if args.dump_outputs and args.steps > 0:
+        name = "enhanced_pcm" if args.frontend else "enhanced_mag"
+        dump_outputs(args.dump_outputs, {name: last}, rank, world)
     frames = B * args.steps
     total_frames, max_elapsed = reduce_throughput(frames, elapsed, dist if world > 1 else None, device)
     proof = collective_proof(frames / elapsed, dist if world > 1 else None, device)
@@ -547,19 +587,19 @@ def main():
             "collective": {"backend": proof["backend"], "ranks_reduced": proof["ranks_reduced"],
                            "per_rank_frames_per_s": [round(x, 1) for x in proof["per_rank"]]},
         }
-        if not selftest:
+        if not selftest and args.full:
             line.update(kernel_report(args, eng, pool, out, B, mode))
         if args.host_io:
             line["step_latency_ms"] = line["ms_per_step"]
             line["real_time_budget_ms"] = 16.0
             line["host_memory"] = "page-locked (nutls_host_alloc)" if pin_in is not None else "pageable"
-        if not selftest and not args.no_cpu_baseline and args.variant == "lstm" and args.ctfa_mode == "frame":
+        if args.full and not selftest and not args.no_cpu_baseline and args.variant == "lstm" and args.ctfa_mode == "frame":
             import nunet_amd
             line["cpu_baseline"] = cpu_baseline()
             line["parity_rms_vs_oracle"] = parity_check(nunet_amd.NutlsEngine, pool_host)
         default_run = (not selftest and world == 1 and mode == "fused" and args.variant == "lstm" and args.batch == 256
                        and not (args.host_io or args.frontend) and args.ctfa_mode == "frame")
-        if default_run and not args.no_other_configs:
+        if args.full and default_run and not args.no_other_configs:
             eng.close()
             line["other_configs"] = other_config_records(local_rank)
         print(json.dumps(line))

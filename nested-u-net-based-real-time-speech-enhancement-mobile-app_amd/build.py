@@ -24,6 +24,10 @@ if os.environ.get("NUTLS_BUILD_G4_PROF") == "1":      # developer knob: the prof
     SOURCES.insert(3, "fused_step_g4_prof.hip")
 # (headers are found by scanning the #include "..." lines of every source: _deps)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+# The 4-stream packed kernel is one very large function, and LLVM's SDWA peephole (which only re-encodes sub-dword operand
+# selects) spent over a third of its compile time on it: 24 minutes with it, 12 without, and it alone sets the length of a clean
+# build.  It is compiled without the pass; its results are bit-identical (its step at 1024 streams ~1 % slower; no default plan).
+SOURCE_FLAGS = {"fused_step_g4.hip": ["-mllvm", "-amdgpu-sdwa-peephole=0"], "fused_step_g4_prof.hip": ["-mllvm", "-amdgpu-sdwa-peephole=0"]}
 LAST_BUILD = None      # what the last build() call did: {"mode", "rebuilt": [...], "sources", "seconds", "linked"}
 
 
@@ -54,14 +58,31 @@ def _deps(path: str, seen=None) -> set:
     return seen
 
 
+def _flags(src: str) -> list:
+    return FLAGS + SOURCE_FLAGS.get(src, [])
+
+
+def _flags_stamp(src: str) -> str:
+    """The flags an object was compiled with, beside it: an object compiled with other flags is stale too."""
+    return _obj(src) + ".flags"
+
+
 def _stale_sources(force: bool):
     out = []
     for s in SOURCES:
         o = _obj(s)
         dep = max(os.path.getmtime(d) for d in _deps(os.path.join(CSRC, s)))
-        if force or not os.path.exists(o) or os.path.getmtime(o) < dep:
+        stamp = _flags_stamp(s)
+        same_flags = os.path.exists(stamp) and open(stamp).read() == " ".join(_flags(s))
+        if force or not os.path.exists(o) or os.path.getmtime(o) < dep or not same_flags:
             out.append(s)
     return out
+
+
+def _compile(hipcc: str, src: str, verbose: bool):
+    _run([hipcc] + _flags(src) + ["-c", os.path.join(CSRC, src), "-o", _obj(src)], verbose)
+    with open(_flags_stamp(src), "w") as f:
+        f.write(" ".join(_flags(src)))
 
 
 def _run(cmd, verbose):
@@ -89,10 +110,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return LIB
     import time
     t0 = time.time()
-    # (the longest compiles first: the 4-stream packed kernel alone is 12 minutes, the pool must not start it last)
+    # (the longest compiles first: the 4-stream packed kernel alone is about 12 minutes, the pool must not start it last)
     order = sorted(todo, key=lambda s: {"fused_step_g4.hip": 0, "fused_step_g4_prof.hip": 0, "fused_step_g2.hip": 1}.get(s, 2))
     with ThreadPoolExecutor(max_workers=6) as ex:
-        list(ex.map(lambda s: _run([hipcc] + FLAGS + ["-c", os.path.join(CSRC, s), "-o", _obj(s)], verbose), order))
+        list(ex.map(lambda s: _compile(hipcc, s, verbose), order))
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + [_obj(s) for s in SOURCES], verbose)
     LAST_BUILD = {"mode": "force" if force else "incremental", "rebuilt": list(todo), "sources": len(SOURCES), "seconds": round(time.time() - t0, 1), "linked": True}
     print("nutls build: rebuilt %d of %d sources (%s) and linked in %.0f s" % (len(todo), len(SOURCES), ", ".join(todo) or "-", time.time() - t0), flush=True)

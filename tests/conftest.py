@@ -10,7 +10,6 @@ if ROOT not in sys.path:
 import nunet_amd  # noqa: E402,F401  (registers the package alias)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE_TFLITE = "/root/reference/dnn_model/tflite/nutls_lstm.tflite"
 
 
 def pytest_configure(config):
@@ -22,7 +21,3 @@ def pytest_configure(config):
 def golden_dir():
     return GOLDEN
 
-
-@pytest.fixture(scope="session")
-def has_reference():
-    return os.path.exists(REFERENCE_TFLITE)

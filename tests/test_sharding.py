@@ -153,3 +153,46 @@ def test_bench_py_defines_every_entry_its_main_dispatches_to():
     import bench
     for fn in ("bench_offline", "other_config_records", "cpu_baseline", "kernel_report", "parity_check", "self_launch"):
         assert callable(getattr(bench, fn)), fn
+
+
+@pytest.mark.timeout(300)
+def test_bench_py_dump_outputs_one_rank(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned (here the stand-in engine's 0.5 * input of step
+    K - 1, pool slot (K - 1) % 8) as float32; `--steps` is the number of timed steps and the line holds `ms_per_step`."""
+    import json
+    import subprocess
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "dump"
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--selftest-launcher", "--dump-outputs", str(d)]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, env=env, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["timed_window_ms"] / 3 - j["ms_per_step"]) < 1e-3
+    assert sorted(os.listdir(d)) == ["enhanced_mag.npy"]
+    got = np.load(d / "enhanced_mag.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 256)
+    np.testing.assert_array_equal(got, 0.5 * bench.synthetic_pool(4, 8, 1234)[(3 - 1) % 8])
+
+
+def test_dump_outputs_budget_covers_all_ranks_and_one_utterance_outputs(tmp_path, monkeypatch):
+    """The 64 MB budget holds for DIR as a whole (each of N ranks gets 1 / N of it) and also for an output whose leading axis is 1
+    (one offline utterance, [1, T, 256]): rows of the array as [-1, last axis] are sampled, with a fixed seed."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    x = np.arange(1 * 4096 * 256, dtype=np.float32).reshape(1, 4096, 256)          # 4 MB
+    for rank in range(2):
+        bench.dump_outputs(str(tmp_path), {"enhanced_mag": x}, rank, 2)
+    total = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path) if not f.endswith("_rows.npy"))
+    assert total <= (1 << 20) + 2 * 256
+    a, rows = np.load(tmp_path / "enhanced_mag_rank0.npy"), np.load(tmp_path / "enhanced_mag_rank0_rows.npy")
+    assert a.shape == (512, 256) and rows.shape == (512,) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(a, x.reshape(-1, 256)[rows.astype(np.int64)])
+    np.testing.assert_array_equal(a, np.load(tmp_path / "enhanced_mag_rank1.npy"))          # same seed, same rows

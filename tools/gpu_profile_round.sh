@@ -11,9 +11,9 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 KPAT=nutls_fused_step; [ "$VARIANT" = baseline ] && KPAT=nutls_fused_base_step
 # 1. bench line (with the CPU baseline leg) and the timeline
-( cd $R && timeout 900 python bench.py --mode $MODE --variant $VARIANT --profile-json $OUT/timeline.json > $OUT/bench.json 2> $OUT/bench.err )
+( cd $R && timeout -k 10 900 python bench.py --full --mode $MODE --variant $VARIANT --profile-json $OUT/timeline.json > $OUT/bench.json 2> $OUT/bench.err ) || exit $?
 # 2. kernel trace of the same command
-rm -rf /tmp/kt; ( cd $R && timeout 600 rocprofv3 --kernel-trace -d /tmp/kt -o kt -- python bench.py --mode $MODE --variant $VARIANT --no-cpu-baseline > /dev/null 2>&1 )
+rm -rf /tmp/kt; ( cd $R && timeout -k 10 600 rocprofv3 --kernel-trace -d /tmp/kt -o kt -- python bench.py --full --mode $MODE --variant $VARIANT --no-cpu-baseline > /dev/null 2>&1 ) || exit $?
 python $R/tools/rocprof_summary.py $(find /tmp/kt -name "*.db" | head -1) > $OUT/kernel_stats.txt
 # 3. PMC passes
 {
@@ -23,6 +23,6 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS S
 done
 } > $OUT/pmc.txt 2>&1
 python $R/tools/pmc_traffic.py $OUT/pmc.txt $MODE 256 $VARIANT > $OUT/pmc_traffic.json
-[ "$VARIANT" = lstm ] && ( cd $R && { timeout 300 python bench.py --no-cpu-baseline --variant baseline; timeout 300 python bench.py --no-cpu-baseline --batch 1024 --host-io --steps 100; timeout 300 python bench.py --no-cpu-baseline --batch 2048 --steps 50; timeout 300 python bench.py --no-cpu-baseline --frontend; timeout 300 python bench.py --no-cpu-baseline --offline 1024 --steps 20; } > $OUT/bench_other_configs.json 2>/dev/null )
+if [ "$VARIANT" = lstm ]; then ( cd $R && { timeout -k 10 300 python bench.py --full --no-cpu-baseline --variant baseline && timeout -k 10 300 python bench.py --full --no-cpu-baseline --batch 1024 --host-io --steps 100 && timeout -k 10 300 python bench.py --full --no-cpu-baseline --batch 2048 --steps 50 && timeout -k 10 300 python bench.py --full --no-cpu-baseline --frontend && timeout -k 10 300 python bench.py --full --no-cpu-baseline --offline 1024 --steps 20; } > $OUT/bench_other_configs.json 2>/dev/null ) || exit $?; fi
 [ -f $OUT/bench_other_configs.json ] && cut -c1-330 $OUT/bench_other_configs.json
 tail -1 $OUT/bench.json | cut -c1-900; head -5 $OUT/kernel_stats.txt; cat $OUT/pmc.txt; cat $OUT/pmc_traffic.json
