@@ -111,6 +111,20 @@ int nutls_enhance_hop_host(nutls_handle* h, const float* pcm_in, float* pcm_out,
  * (+ phase kept inside), synthesis of one hop from the library's mag_out buffer.  Device pointers. */
 int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream);
 int nutls_istft_hop(nutls_handle* h, float* pcm_out, int dc_mode, void* stream);
+/* Waveform block mode: the same front end / back end for OFFLINE handles (nutls_create_offline, nutls_create_offline_batch; a streaming
+ * handle gets NUTLS_ERR_ARG), a whole block per call -- the loop of interpreter_proposed.py:203-213, 352-365 over n_hops hops of every
+ * utterance in one analysis launch and one synthesis launch around nutls_process_block.
+ * pcm_in / pcm_out: DEVICE [utterances, n_hops * 256] float32 (8-byte aligned), 1 <= n_hops <= max_frames.  Analysis of n_hops hops of
+ * every utterance -> nutls_process_block on the library's buffers -> synthesis; asynchronous on `stream`.  Like nutls_enhance_hop the
+ * output lags the input by one hop.  Previous hop and overlap tail are carried per utterance from call to call, so a recording may be
+ * cut into blocks of any lengths (the result does not depend on the cut); nutls_reset(h, u) zeroes utterance u's (-1: everybody's). */
+int nutls_enhance_block(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, int dc_mode, void* stream);
+/* Same with HOST buffers (pageable or nutls_host_alloc); synchronises. */
+int nutls_enhance_block_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, int dc_mode);
+/* The two halves on their own.  mag: DEVICE [utterances, n_hops, 256] (bins 1..256, the layout nutls_process_block takes); the phasors stay
+ * inside the handle, so the synthesis belongs to the last analysed block and takes the same n_hops. */
+int nutls_stft_block(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, void* stream);
+int nutls_istft_block(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, int dc_mode, void* stream);
 
 /* ---- Offline / block mode ------------------------------------------------
  * One utterance, up to `max_frames` consecutive frames per call: the frame index takes the place of the stream
@@ -203,7 +217,8 @@ int nutls_reset(nutls_handle* h, int stream_idx);
  * tensor per kind) and "input_layer".  Fused mode: these tensors never leave LDS; with nutls_debug_trace(h, 1) every step of a one-stream
  * fused handle (<= 64 streams) runs on the library's profiling build of the step kernel, which copies them out -- "<stage>.y" of all 12
  * stages, "<stage>.up" of the 6 decoder stages, "input_layer" of the LAST step -- for layer-by-layer comparison with a reference trace
- * (tests/test_gpu_trace.py).  Testing / debugging only: the profiling build is a few percent slower. */
+ * (tests/test_gpu_trace.py).  Testing / debugging only: the profiling build is a few percent slower.
+ * Offline handles, waveform block mode: "phasor_block" = the unit phasors of the last analysed block, [utterances, its n_hops, 257, 2]. */
 int nutls_debug_trace(nutls_handle* h, int enable);
 /* Developer knobs of a handle (timing experiments; no effect on results).  "skew": start skew of the fused kernel's workgroups -- workgroup w
  * sleeps (w mod 4) * value * 64 clocks before its first op (0 = off, the default; NUTLS_FUSED_SKEW sets it at creation).  Experiment builds

@@ -138,6 +138,12 @@ struct Engine {
   // STFT front / back end (allocated on first use): previous hop, overlap tail, phasors, windows, twiddles, staging
   float *fe_tail = nullptr, *fe_ola = nullptr, *fe_ph = nullptr, *fe_win = nullptr, *fe_inv = nullptr, *fe_tw = nullptr;
   float *fe_pcm_in = nullptr, *fe_pcm_out = nullptr;
+  // waveform block mode of an offline handle (stft_block.hip; allocated on first use): previous hop and overlap tail of every utterance [outt][256],
+  // two buffers each -- a launch reads [par] and writes [1 - par] --, the phasors of the last analysed block [outt][fb_hops][257] float2, windows,
+  // twiddles (stft_block_twiddles) and, for the host entry, PCM staging [outt][offline * 256]
+  float *fb_tail[2] = {nullptr, nullptr}, *fb_ola[2] = {nullptr, nullptr}, *fb_ph = nullptr, *fb_win = nullptr, *fb_inv = nullptr, *fb_tw = nullptr;
+  float *fb_pcm_in = nullptr, *fb_pcm_out = nullptr;
+  int fb_tail_par = 0, fb_ola_par = 0, fb_hops = 0;
   float *t_inlayer = nullptr, *t_y = nullptr, *t_d = nullptr, *t_up = nullptr;
   float* upcat[6] = {nullptr};
   int offline = 0;       // > 0: offline / block handle for up to this many frames per call (arena slot 0 = carried state)
@@ -1048,6 +1054,28 @@ struct nutls_handle {
 };
 
 // ---- STFT front / back end state ---------------------------------------------------------------
+// windows in float32 like tf.signal.hann_window (interpreter_proposed.py:20-26); twiddles e^{-2 pi i k / 512}, k = 0..255, from double
+static void frontend_tables(std::vector<float>* win_out, std::vector<float>* inv_out, std::vector<float>* tw_out) {
+  std::vector<float> hann(NUTLS_FRAME_LEN), win(NUTLS_FRAME_LEN), inv(NUTLS_FRAME_LEN), tw(NUTLS_FRAME_LEN);
+  for (int k = 0; k < NUTLS_FRAME_LEN; ++k) {
+    const float arg = 6.28318530717958647692f * static_cast<float>(k) / static_cast<float>(NUTLS_FRAME_LEN);
+    hann[k] = 0.5f - 0.5f * std::cos(arg);
+  }
+  win = hann;
+  win[0] = 1e-7f; win[NUTLS_FRAME_LEN - 1] = 1e-7f;
+  for (int k = 0; k < NUTLS_FRAME_LEN; ++k) {
+    const int k2 = (k + NUTLS_FRAME_STEP) % NUTLS_FRAME_LEN;
+    inv[k] = hann[k] / (hann[k] * hann[k] + hann[k2] * hann[k2]);
+  }
+  for (int k = 0; k < NUTLS_FRAME_LEN / 2; ++k) {
+    const double a = -2.0 * 3.14159265358979323846 * k / NUTLS_FRAME_LEN;
+    tw[2 * k] = static_cast<float>(std::cos(a));
+    tw[2 * k + 1] = static_cast<float>(std::sin(a));
+  }
+  *win_out = win; *inv_out = inv;
+  if (tw_out) *tw_out = tw;
+}
+
 static int frontend_init(Engine* e) {
   if (e->fe_tail) return NUTLS_OK;
   const size_t hop = static_cast<size_t>(e->B) * NUTLS_FRAME_STEP;
@@ -1065,27 +1093,68 @@ static int frontend_init(Engine* e) {
       (rc = dalloc(&e->fe_win, NUTLS_FRAME_LEN)) || (rc = dalloc(&e->fe_inv, NUTLS_FRAME_LEN)) || (rc = dalloc(&e->fe_tw, NUTLS_FRAME_LEN)) ||
       (rc = dalloc(&e->fe_pcm_in, hop)) || (rc = dalloc(&e->fe_pcm_out, hop)))
     return rc;
-  // windows in float32 like tf.signal.hann_window (interpreter_proposed.py:20-26); twiddles from double
-  std::vector<float> hann(NUTLS_FRAME_LEN), win(NUTLS_FRAME_LEN), inv(NUTLS_FRAME_LEN), tw(NUTLS_FRAME_LEN);
-  for (int k = 0; k < NUTLS_FRAME_LEN; ++k) {
-    const float arg = 6.28318530717958647692f * static_cast<float>(k) / static_cast<float>(NUTLS_FRAME_LEN);
-    hann[k] = 0.5f - 0.5f * std::cos(arg);
-  }
-  win = hann;
-  win[0] = 1e-7f; win[NUTLS_FRAME_LEN - 1] = 1e-7f;
-  for (int k = 0; k < NUTLS_FRAME_LEN; ++k) {
-    const int k2 = (k + NUTLS_FRAME_STEP) % NUTLS_FRAME_LEN;
-    inv[k] = hann[k] / (hann[k] * hann[k] + hann[k2] * hann[k2]);
-  }
-  for (int k = 0; k < NUTLS_FRAME_LEN / 2; ++k) {
-    const double a = -2.0 * 3.14159265358979323846 * k / NUTLS_FRAME_LEN;
-    tw[2 * k] = static_cast<float>(std::cos(a));
-    tw[2 * k + 1] = static_cast<float>(std::sin(a));
-  }
+  std::vector<float> win, inv, tw;
+  frontend_tables(&win, &inv, &tw);
   HIP_TRY(hipMemcpy(e->fe_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->fe_inv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->fe_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
   e->fe_tail = tail;
+  return NUTLS_OK;
+}
+
+// ---- waveform block mode: front / back end state of an offline handle ---------------------------
+// (an offline handle's B counts arena slots, utterances x (max_frames + 1): frontend_init's per-stream buffers are not its shape)
+static int frontend_block_init(Engine* e) {
+  if (e->fb_tw) return NUTLS_OK;
+  const size_t hop = static_cast<size_t>(e->outt) * NUTLS_FRAME_STEP;
+  int rc;
+  float* twd = nullptr;
+  const std::vector<float> tw = stft_block_twiddles();
+  if ((rc = dev_alloc(e, hop, &e->fb_tail[0], true)) || (rc = dev_alloc(e, hop, &e->fb_tail[1], true)) || (rc = dev_alloc(e, hop, &e->fb_ola[0], true)) ||
+      (rc = dev_alloc(e, hop, &e->fb_ola[1], true)) ||
+      (rc = dev_alloc(e, static_cast<size_t>(e->outt) * e->offline * (NUTLS_FRAME_STEP + 1) * 2, &e->fb_ph, true)) ||
+      (rc = dev_alloc(e, NUTLS_FRAME_LEN, &e->fb_win, false)) || (rc = dev_alloc(e, NUTLS_FRAME_LEN, &e->fb_inv, false)) || (rc = dev_alloc(e, tw.size(), &twd, false)))
+    return rc;
+  std::vector<float> win, inv;
+  frontend_tables(&win, &inv, nullptr);
+  HIP_TRY(hipMemcpy(e->fb_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->fb_inv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(twd, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+  e->fb_tw = twd;
+  return NUTLS_OK;
+}
+
+// common argument checks of the four block entries; `who` names the entry in the message
+static int block_args(nutls_handle* h, bool pointers_ok, int n_hops, const char* who) {
+  if (!h || !pointers_ok) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  const Engine* e = &h->eng;
+  if (!e->offline)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": not an offline handle (nutls_create_offline); a streaming handle takes PCM hop by hop through nutls_enhance_hop");
+  if (n_hops < 1 || n_hops > e->offline) return fail(NUTLS_ERR_ARG, std::string(who) + ": n_hops out of range (1 .. max_frames)");
+  return NUTLS_OK;
+}
+
+static int block_dc(int dc_mode, const char* who) {
+  if (dc_mode != NUTLS_DC_EDGE && dc_mode != NUTLS_DC_ZERO) return fail(NUTLS_ERR_ARG, std::string(who) + ": dc_mode must be NUTLS_DC_EDGE or NUTLS_DC_ZERO");
+  return NUTLS_OK;
+}
+
+static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_hops, hipStream_t s) {
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = frontend_block_init(e)) return rc;
+  HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, e->outt, n_hops, s));
+  e->fb_tail_par ^= 1;
+  e->fb_hops = n_hops;
+  return NUTLS_OK;
+}
+
+static int istft_block_launch(Engine* e, const float* mag, float* pcm_out, int n_hops, int dc_mode, hipStream_t s) {
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = frontend_block_init(e)) return rc;
+  if (n_hops != e->fb_hops) return fail(NUTLS_ERR_ARG, "nutls_istft_block: n_hops differs from the block the phasors inside the handle belong to (nutls_stft_block first)");
+  HIP_TRY(launch_istft_block(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
+                             dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->outt, n_hops, s));
+  e->fb_ola_par ^= 1;
   return NUTLS_OK;
 }
 
@@ -1661,6 +1730,47 @@ int nutls_enhance_hop_host(nutls_handle* h, const float* pcm_in, float* pcm_out,
   return NUTLS_OK;
 }
 
+int nutls_stft_block(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, void* stream) {
+  if (int rc = block_args(h, pcm_in && mag, n_hops, "nutls_stft_block")) return rc;
+  return stft_block_launch(&h->eng, pcm_in, mag, n_hops, static_cast<hipStream_t>(stream));
+}
+
+int nutls_istft_block(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, int dc_mode, void* stream) {
+  if (int rc = block_args(h, mag && pcm_out, n_hops, "nutls_istft_block")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_istft_block")) return rc;
+  return istft_block_launch(&h->eng, mag, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream));
+}
+
+int nutls_enhance_block(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, int dc_mode, void* stream) {
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_enhance_block")) return rc;
+  Engine* e = &h->eng;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // analysis, model and synthesis follow each other on the caller's stream: the chunk streams of the block pipeline fork from it behind the
+  // analysis and have joined it again when nutls_process_block returns
+  if (int rc = stft_block_launch(e, pcm_in, e->io_in, n_hops, s)) return rc;
+  if (int rc = nutls_process_block(h, e->io_in, e->io_out, n_hops, stream)) return rc;
+  return istft_block_launch(e, e->io_out, pcm_out, n_hops, dc_mode, s);
+}
+
+int nutls_enhance_block_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, int dc_mode) {
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_host")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_enhance_block_host")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->fb_pcm_in) {
+    const size_t n = static_cast<size_t>(e->outt) * e->offline * NUTLS_FRAME_STEP;
+    if (int rc = dev_alloc(e, n, &e->fb_pcm_out, false)) return rc;
+    if (int rc = dev_alloc(e, n, &e->fb_pcm_in, false)) return rc;
+  }
+  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * NUTLS_FRAME_STEP * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(e->fb_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = nutls_enhance_block(h, e->fb_pcm_in, e->fb_pcm_out, n_hops, dc_mode, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->fb_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return NUTLS_OK;
+}
+
 int nutls_state_count(nutls_handle* h) { return h ? static_cast<int>(h->eng.states.size()) : fail(NUTLS_ERR_ARG, "null handle"); }
 
 int nutls_state_info(nutls_handle* h, int index, const char** name, int* dim0, int* dim1) {
@@ -1827,6 +1937,13 @@ int nutls_reset(nutls_handle* h, int stream_idx) {
       HIP_TRY(hipMemset(e->fe_ola + static_cast<size_t>(NUTLS_FRAME_STEP) * stream_idx, 0, hop));
     }
   }
+  if (e->fb_tw) {   // waveform block mode of an offline handle: the utterance's (all utterances') previous hop and overlap tail, both buffers of each
+    const size_t hop = NUTLS_FRAME_STEP * sizeof(float);
+    for (float* p : {e->fb_tail[0], e->fb_tail[1], e->fb_ola[0], e->fb_ola[1]}) {
+      if (utt < 0) HIP_TRY(hipMemset(p, 0, hop * e->outt));
+      else HIP_TRY(hipMemset(p + static_cast<size_t>(NUTLS_FRAME_STEP) * utt, 0, hop));
+    }
+  }
   HIP_TRY(hipDeviceSynchronize());
   return NUTLS_OK;
 }
@@ -1834,6 +1951,15 @@ int nutls_reset(nutls_handle* h, int stream_idx) {
 int nutls_debug_get(nutls_handle* h, const char* name, float* host_buf, size_t n_floats) {
   if (!h || !name || !host_buf) return fail(NUTLS_ERR_ARG, "nutls_debug_get: null pointer");
   Engine* e = &h->eng;
+  if (std::string(name) == "phasor_block") {      // offline handles: the phasors of the last analysed block, [utterances, its n_hops, 257, 2]
+    if (!e->offline) return fail(NUTLS_ERR_ARG, "debug tensor phasor_block: not an offline handle");
+    if (!e->fb_ph || !e->fb_hops) return fail(NUTLS_ERR_ARG, "debug tensor not allocated yet: phasor_block");
+    if (n_floats != static_cast<size_t>(e->outt) * e->fb_hops * (NUTLS_FRAME_STEP + 1) * 2) return fail(NUTLS_ERR_ARG, "size mismatch for debug tensor phasor_block");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host_buf, e->fb_ph, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return NUTLS_OK;
+  }
   {   // the I/O staging buffers and the STFT phasors are plain [B, n] arrays
     const std::string nm(name);
     const float* src = nullptr;

@@ -202,6 +202,15 @@ constexpr int NUTLS_FRAME_STEP = 256;   // interpreter_proposed.py:18
 hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s);
 hipError_t launch_istft_hop(const float* est, const float* ph, const float* inv_win, const float* tw, float* ola, float* pcm_out,
                             int dc_edge, int B, hipStream_t s);
+// Waveform block mode of the offline handles (stft_block.hip): the same analysis / synthesis for n_hops consecutive hops of each of U
+// utterances in one launch.  pcm / pcm_out [U][n_hops * 256]; mag / est [U][n_hops][256]; ph [U][n_hops][257] float2.  The carried previous hop
+// (tail) and overlap tail (ola), [U][256], are read from *_in and written to *_out: two buffers each, since the first tile of an utterance reads
+// what its last tile replaces.  win / inv_win as above; tw = stft_block_twiddles() on the device.
+std::vector<float> stft_block_twiddles();
+hipError_t launch_stft_block(const float* pcm, const float* tail_in, float* tail_out, const float* win, const float* tw, float* mag, float* ph,
+                             int U, int n_hops, hipStream_t s);
+hipError_t launch_istft_block(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
+                              float* pcm_out, int dc_edge, int U, int n_hops, hipStream_t s);
 // (Rounds 1-3 kept a third kernel family here: a persistent plan-interpreter kernel, megakernel.hip, execution mode 2 -- retired in
 //  round 4: the fused kernel is the one-launch path, the per-layer kernels below are the cross-check and the block mode.)
 

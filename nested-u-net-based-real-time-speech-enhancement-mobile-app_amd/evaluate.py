@@ -38,10 +38,18 @@ def _read(path: str) -> np.ndarray:
     return x.astype(np.float64)
 
 
-def evaluate_directory(directory: str, out_dir: Optional[str] = None, dc_mode: str = "edge", device: int = 0) -> List[Dict[str, float]]:
+ENGINES = ("stream", "block")
+
+
+def evaluate_directory(directory: str, out_dir: Optional[str] = None, dc_mode: str = "edge", device: int = 0,
+                       engine: str = "stream") -> List[Dict[str, float]]:
     """All pairs of ``directory`` in ONE batched engine (one stream per clip; shorter clips are zero-padded to the
-    longest and scored on their own length).  Returns one dict per clip; optionally writes ``<name>_enhanced.wav``."""
-    from .runner import NutlsEngine
+    longest and scored on their own length).  Returns one dict per clip; optionally writes ``<name>_enhanced.wav``.
+    ``engine``: "stream" (default) -- a streaming engine fed hop by hop (:func:`stream_enhance.enhance_batch_on_device`);
+    "block" -- an offline handle fed blocks of up to 1024 hops (:func:`stream_enhance.enhance_utterances_offline`)."""
+    if engine not in ENGINES:
+        raise ValueError("engine must be one of %s, got %r" % (list(ENGINES), engine))
+    from .runner import NutlsEngine, NutlsOffline
     pairs = find_pairs(directory)
     if not pairs:
         raise ValueError("no <name>_0.wav / <name>.wav pairs in %s" % directory)
@@ -51,11 +59,19 @@ def evaluate_directory(directory: str, out_dir: Optional[str] = None, dc_mode: s
     batch = np.zeros((len(pairs), n_max), np.float32)
     for i, x in enumerate(noisy):
         batch[i, :len(x)] = x
-    eng = NutlsEngine(batch=len(pairs), device=device)
-    try:
-        enhanced = SE.enhance_batch_on_device(batch, eng, dc_mode)
-    finally:
-        eng.close()
+    if engine == "block":
+        hops = (n_max - (SE.FRAME_LEN - SE.FRAME_STEP)) // SE.FRAME_STEP
+        off = NutlsOffline(utterances=len(pairs), max_frames=max(1, min(1024, hops)), device=device)
+        try:
+            enhanced = SE.enhance_utterances_offline(batch, off, dc_mode)
+        finally:
+            off.close()
+    else:
+        eng = NutlsEngine(batch=len(pairs), device=device)
+        try:
+            enhanced = SE.enhance_batch_on_device(batch, eng, dc_mode)
+        finally:
+            eng.close()
     rows = []
     for i, p in enumerate(pairs):
         n = min(len(noisy[i]), len(clean[i]))

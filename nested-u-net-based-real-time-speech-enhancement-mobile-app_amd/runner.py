@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "nutls_fused_blob_floats", "nutls_fused_pack_blob", "nutls_state_get_all", "nutls_offline_set_ctfa_mode",
     "nutls_offline_set_pipeline", "nutls_streams_per_workgroup", "nutls_fused_plan_blob_floats", "nutls_fused_pack_blob_plan",
     "nutls_set_ctfa_mode", "nutls_fused_plan_num_ops", "nutls_fused_plan_op_info", "nutls_create_plan",
+    "nutls_enhance_block", "nutls_enhance_block_host", "nutls_stft_block", "nutls_istft_block",
 )
 
 
@@ -101,6 +102,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nutls_enhance_hop_host.argtypes = [c.c_void_p, fp, fp, c.c_int]
     lib.nutls_stft_hop.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p]
     lib.nutls_istft_hop.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_enhance_block"):
+        lib.nutls_enhance_block.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p]
+        lib.nutls_enhance_block_host.argtypes = [c.c_void_p, fp, fp, c.c_int, c.c_int]
+        lib.nutls_stft_block.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]
+        lib.nutls_istft_block.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -565,6 +571,126 @@ class NutlsOffline:
         stream = torch.cuda.current_stream(mag.device).cuda_stream
         _check(self._lib, self._lib.nutls_process_block(self._h, mag.data_ptr(), out.data_ptr(), int(shape[-2]), stream))
         return out
+
+    # -- waveform block mode: STFT / inverse STFT + overlap-add of whole blocks on the device (csrc/stft_block.hip) --------------
+    _DC = {"edge": 0, "zero": 1}
+
+    def _dc(self, dc_mode: str) -> int:
+        if dc_mode not in self._DC:
+            raise ValueError("dc_mode must be 'edge' or 'zero'")
+        return self._DC[dc_mode]
+
+    @staticmethod
+    def _cuda_f32(x, name: str):
+        import torch
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor" % name)
+        return x
+
+    def _pcm_hops(self, pcm, name: str = "pcm") -> int:
+        self._cuda_f32(pcm, name)
+        shape = tuple(pcm.shape)
+        ok = (pcm.dim() == 2 and shape[0] == self.utterances) or (pcm.dim() == 1 and self.utterances == 1)
+        if not ok or shape[-1] % 256 or not 1 <= shape[-1] // 256 <= self.max_frames:
+            raise ValueError("%s must be [%sn_hops*256] with 1 <= n_hops <= %d, got %s" % (
+                name, "%d," % self.utterances if self.utterances > 1 else "", self.max_frames, shape))
+        return shape[-1] // 256
+
+    def _mag_hops(self, mag, name: str = "mag") -> int:
+        self._cuda_f32(mag, name)
+        shape = tuple(mag.shape)
+        ok = (mag.dim() == 3 and shape[0] == self.utterances) or (mag.dim() == 2 and self.utterances == 1)
+        if not ok or shape[-1] != T.N_BINS or not 1 <= shape[-2] <= self.max_frames:
+            raise ValueError("%s must be [%s1<=n<=%d,%d], got %s" % (
+                name, "%d," % self.utterances if self.utterances > 1 else "", self.max_frames, T.N_BINS, shape))
+        return shape[-2]
+
+    def enhance_block_device(self, pcm, out=None, dc_mode: str = "edge"):
+        """One block of PCM on device tensors: ``pcm [n_hops*256]`` (one utterance) or ``[utterances, n_hops*256]`` float32 CUDA tensor,
+        n_hops <= max_frames -> the enhanced PCM of the same shape, one hop late like ``NutlsEngine.enhance_hop``
+        (``nutls_enhance_block``: analysis, ``process_block``, synthesis); asynchronous on the current torch stream."""
+        import torch
+        dc = self._dc(dc_mode)
+        n = self._pcm_hops(pcm)
+        if out is None:
+            out = torch.empty_like(pcm)
+        elif self._cuda_f32(out, "out").shape != pcm.shape or out.device != pcm.device:
+            raise ValueError("out must have pcm's shape and device")
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        _check(self._lib, self._lib.nutls_enhance_block(self._h, pcm.data_ptr(), out.data_ptr(), n, dc, stream))
+        return out
+
+    def stft_block_device(self, pcm, out=None):
+        """Analysis half only: ``pcm`` as in :meth:`enhance_block_device` -> magnitudes of bins 1..256, ``[n_hops,256]`` /
+        ``[utterances,n_hops,256]`` (what :meth:`process_block_device` takes); the phase stays inside the handle
+        (``debug_get("phasor_block", (n_hops, 257, 2))``)."""
+        import torch
+        n = self._pcm_hops(pcm)
+        shape = tuple(pcm.shape[:-1]) + (n, T.N_BINS)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=pcm.device)
+        elif tuple(self._cuda_f32(out, "out").shape) != shape or out.device != pcm.device:
+            raise ValueError("out must be %s on pcm's device" % (shape,))
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        _check(self._lib, self._lib.nutls_stft_block(self._h, pcm.data_ptr(), out.data_ptr(), n, stream))
+        return out
+
+    def istft_block_device(self, mag, out=None, dc_mode: str = "edge"):
+        """Synthesis half only: magnitudes ``[n_hops,256]`` / ``[utterances,n_hops,256]`` with the phase of the last
+        :meth:`stft_block_device` of the same ``n_hops`` -> PCM ``[n_hops*256]`` / ``[utterances,n_hops*256]``, overlap-added."""
+        import torch
+        dc = self._dc(dc_mode)
+        n = self._mag_hops(mag)
+        shape = tuple(mag.shape[:-2]) + (n * 256,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=mag.device)
+        elif tuple(self._cuda_f32(out, "out").shape) != shape or out.device != mag.device:
+            raise ValueError("out must be %s on mag's device" % (shape,))
+        stream = torch.cuda.current_stream(mag.device).cuda_stream
+        _check(self._lib, self._lib.nutls_istft_block(self._h, mag.data_ptr(), out.data_ptr(), n, dc, stream))
+        return out
+
+    def enhance_block_host(self, pcm: np.ndarray, out: Optional[np.ndarray] = None, dc_mode: str = "edge") -> np.ndarray:
+        """One block on host arrays (pageable or from ``host_alloc``): ``pcm [utterances, n_hops*256]`` float32 contiguous,
+        n_hops <= max_frames (``nutls_enhance_block_host``; synchronous)."""
+        dc = self._dc(dc_mode)
+        if not (isinstance(pcm, np.ndarray) and pcm.dtype == np.float32 and pcm.flags.c_contiguous and pcm.ndim == 2
+                and pcm.shape[0] == self.utterances and pcm.shape[1] % 256 == 0):
+            raise ValueError("pcm must be a contiguous float32 array [%d, n_hops*256], got %s" % (self.utterances, np.shape(pcm)))
+        if out is None:
+            out = np.empty_like(pcm)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == pcm.shape):
+            raise ValueError("out must be a contiguous float32 numpy array of pcm's shape")
+        _check(self._lib, self._lib.nutls_enhance_block_host(self._h, _fptr(pcm), _fptr(out), pcm.shape[1] // 256, dc))
+        return out
+
+    def enhance(self, wave, dc_mode: str = "edge") -> np.ndarray:
+        """``wave [N]`` (one utterance) or ``[utterances, N]`` float, any N -> the enhanced waveform of the same shape, in the alignment
+        of ``stream_enhance.enhance_batch_on_device`` / ``real_time_speech_enhancer`` (the first output hop, the leading half window,
+        is dropped: interpreter_proposed.py:368).  ``(N - 256) // 256`` hops run in blocks of ``max_frames`` through
+        ``nutls_enhance_block_host``; previous hop, overlap tail and model state carry on into the next call until :meth:`reset`."""
+        self._dc(dc_mode)
+        x = np.asarray(wave, dtype=np.float32)
+        batched = x.ndim == 2
+        if x.ndim == 1 and self.utterances == 1:
+            x = x[None]
+        if x.ndim != 2 or x.shape[0] != self.utterances:
+            raise ValueError("wave must be [%sN], got %s" % ("%d," % self.utterances if self.utterances > 1 else "", np.shape(wave)))
+        n = x.shape[1]
+        hops = max(0, (n - 256) // 256)
+        out = np.zeros((self.utterances, n + 256), np.float64)
+        for a in range(0, hops, self.max_frames):
+            b = min(hops, a + self.max_frames)
+            blk = np.ascontiguousarray(x[:, a * 256:b * 256])
+            out[:, a * 256:b * 256] = self.enhance_block_host(blk, None, dc_mode)
+        out = out[:, 256:]
+        return out if batched else out[0]
+
+    def debug_get(self, name: str, shape) -> np.ndarray:
+        """Debug tensors of the handle, ``[utterances] + shape``: "phasor_block" (``shape = (n_hops, 257, 2)`` of the last analysed block)."""
+        a = np.empty((self.utterances,) + tuple(shape), np.float32)
+        _check(self._lib, self._lib.nutls_debug_get(self._h, name.encode(), _fptr(a), a.size))
+        return a
 
     def state_get(self, name: str) -> np.ndarray:
         """Carried state tensor ``name`` of every utterance, ``[utterances, F, C]`` (``[utterances, 21]`` for h / c)."""

@@ -171,6 +171,19 @@ def enhance_batch_on_device(noisy: np.ndarray, engine, dc_mode: str = "edge") ->
     return out[:, FRAME_LEN - FRAME_STEP:]
 
 
+def enhance_utterances_offline(noisy: np.ndarray, offline, dc_mode: str = "edge") -> np.ndarray:
+    """The counterpart of :func:`enhance_batch_on_device` for a :class:`nunet_amd.runner.NutlsOffline`: ``noisy [U, N]`` (one
+    recording per utterance of the handle, equal lengths) -> enhanced ``[U, N]`` in the same alignment.  Whole blocks of up to
+    ``offline.max_frames`` hops cross the host boundary and every stage -- STFT, model, inverse STFT, overlap-add -- runs once per
+    block on the GPU (``NutlsOffline.enhance`` = ``nutls_enhance_block_host`` of the C ABI)."""
+    audio = np.asarray(noisy, np.float32)
+    if audio.ndim == 1:
+        audio = audio[None]
+    if audio.ndim != 2 or audio.shape[0] != offline.utterances:
+        raise ValueError("need one recording per utterance of the handle: %s vs %d" % (audio.shape, offline.utterances))
+    return np.asarray(offline.enhance(audio, dc_mode)).reshape(audio.shape)
+
+
 def snr_db(clean: np.ndarray, est: np.ndarray) -> float:
     n = min(len(clean), len(est))
     c, e = np.asarray(clean[:n], np.float64), np.asarray(est[:n], np.float64)
