@@ -20,6 +20,7 @@
 
 #include "../../include/nutls.h"
 #include "nutls_internal.hpp"
+#include "fused_host.hpp"
 
 namespace nutls {
 
@@ -167,7 +168,7 @@ struct Engine {
                          // (2 was the plan-interpreter kernel of rounds 1-3, retired)
   float* fz_blob = nullptr;              // weight blob of the fused kernel (plan order)
   int fz_streams_req = 0;                // nutls_create_plan: the caller's choice of plan (0: the library's)
-  int fz_streams = 1;                    // streams per workgroup of the fused plan this handle runs (packed plans 2 / 4: chosen by the cost model in fused_setup or by nutls_create_plan)
+  const FusedPlan* fz_plan = nullptr;    // the fused plan this handle runs: the one-stream plan of its variant, or a packed plan (2 / 4 streams per workgroup: chosen by the cost model in fused_setup or by nutls_create_plan)
   // CTFA frequency branch of the fused kernel (nutls_internal.hpp FzTa): fz_ta_zero = 64 zeros + a dump row (frame mode); causal32 mode of a
   // streaming handle (nutls_set_ctfa_mode): history ring [B][12][32][64] and the per-step sums [B][12][64]
   float *fz_ta_zero = nullptr, *fz_ta_ring = nullptr, *fz_ta_sum = nullptr;
@@ -858,17 +859,18 @@ static int upload_ddb_table(Engine* e) {
 // ---- fused kernel (mode 3): weight blob in plan order + the check that the arena is laid out as the plan says ----
 static int fused_setup(Engine* e, const WeightMap& wm) {
   const int v = e->variant;
-  const bool same_count = static_cast<int>(e->states.size()) == fused_num_states(v);
-  bool ok = same_count && e->sstride >= static_cast<size_t>(fused_arena_floats(v));
-  for (int i = 0; ok && i < fused_num_states(v); ++i) {
+  const FusedPlan& one = *fused_plan(v, 1);      // (every variant has a one-stream plan: the arena is laid out for it)
+  const bool same_count = static_cast<int>(e->states.size()) == one.num_states;
+  bool ok = same_count && e->sstride >= static_cast<size_t>(one.arena_floats);
+  for (int i = 0; ok && i < one.num_states; ++i) {
     const StateTensor& st = e->states[i];
-    const bool ring = i >= fused_num_pingpong(v);        // baseline: the dilated-dense history rings are updated in place
-    ok = st.name_prev == fused_state_name(v, i) && st.buf[0] - e->arena == fused_state_off(v, i) &&
-         st.buf[1] - st.buf[0] == (ring ? 0 : fused_parity_stride(v));
+    const bool ring = i >= one.num_pingpong;        // baseline: the dilated-dense history rings are updated in place
+    ok = st.name_prev == one.states[i].name && st.buf[0] - e->arena == one.states[i].off &&
+         st.buf[1] - st.buf[0] == (ring ? 0 : one.parity_stride);
   }
   const float* scratch[11] = {e->t_inlayer, e->t_y, e->t_d, e->t_up, e->upcat[0], e->upcat[1], e->upcat[2], e->upcat[3], e->upcat[4], e->upcat[5], e->ysum};
-  ok = ok && fused_num_scratch(v) == 11 && e->ysum && e->ysum - e->arena == fused_ys_off(v);
-  for (int i = 0; ok && i < fused_num_scratch(v) && i < 11; ++i) ok = scratch[i] - e->arena == fused_scratch_off(v, i);
+  ok = ok && one.num_scratch == 11 && e->ysum && e->ysum - e->arena == one.ys_off;
+  for (int i = 0; ok && i < one.num_scratch && i < 11; ++i) ok = scratch[i] - e->arena == one.scratch[i].off;
   if (ok && v == NUTLS_VARIANT_BASELINE) ok = e->d_ddb != nullptr && e->ddbs.size() == 26;
   if (!ok) return fail(NUTLS_ERR_ARG, "fused plan (tools/gen_fused_plan.py) does not match the engine's arena layout");
   // Which plan: one stream per workgroup, or a packed plan (two / four streams per workgroup: one weight fetch / conversion and one latency
@@ -885,28 +887,28 @@ static int fused_setup(Engine* e, const WeightMap& wm) {
     const double t_plan[5] = {0.0, 1.0, 1.65, 0.0, 3.44};
     double best = 0.0;
     for (int g : {1, 2, 4}) {
-      if (e->B % g != 0 || !fused_has_plan(v, g)) continue;
+      if (e->B % g != 0 || !fused_plan(v, g)) continue;
       const int wgs = e->B / g, rounds = (wgs + e->n_cu - 1) / e->n_cu;
       const double t = rounds * t_plan[g];
       if (best == 0.0 || t < best * 0.98) { best = t; streams = g; }      // (ties and near-ties: the smaller group)
     }
   }
   if (const char* ev = getenv("NUTLS_FUSED_STREAMS")) streams = atoi(ev);      // (developer override; falls back like the library's own choice)
-  if (streams < 1 || !fused_has_plan(v, streams) || e->B % streams != 0) streams = 1;
+  if (streams < 1 || !fused_plan(v, streams) || e->B % streams != 0) streams = 1;
   if (e->fz_streams_req > 0) {          // nutls_create_plan: the caller's choice wins -- or the call fails, it never silently becomes another plan
-    if (!fused_has_plan(v, e->fz_streams_req))
+    if (!fused_plan(v, e->fz_streams_req))
       return fail(NUTLS_ERR_ARG, "nutls_create_plan: no fused plan with that many streams per workgroup for this variant (plans: 1, 2, 4 for the LSTM variant, 1 for the baseline)");
     if (e->B % e->fz_streams_req != 0)
       return fail(NUTLS_ERR_ARG, "nutls_create_plan: the batch must be a multiple of streams_per_workgroup");
     streams = e->fz_streams_req;
   }
-  if (streams > 1 && (fused_plan_arena_floats(v, streams) != fused_arena_floats(v) || fused_plan_parity_stride(v, streams) != fused_parity_stride(v) ||
-                      fused_plan_ys_off(v, streams) != fused_ys_off(v) || fused_plan_ys_block(v, streams) != fused_ys_block(v)))
+  const FusedPlan& plan = *fused_plan(v, streams);
+  if (plan.arena_floats != one.arena_floats || plan.parity_stride != one.parity_stride || plan.ys_off != one.ys_off || plan.ys_block != one.ys_block)
     return fail(NUTLS_ERR_ARG, "packed fused plan does not share the arena layout of the one-stream plan");
-  e->fz_streams = streams;
+  e->fz_plan = &plan;
   std::vector<float> blob;
   std::string err;
-  if (fused_pack_blob(v, wm, &blob, &err, streams) != FZ_PACK_OK) {
+  if (fused_pack_blob(plan, wm, &blob, &err) != FZ_PACK_OK) {
     // Not packable for the fused kernel -- float conv kernels (no int8 payload), only some of them int8, a scale count that
     // does not match ... -- is not an error of the handle: the per-layer modes only need the de-quantised floats, the handle
     // runs on them (hipGraph replay, mode 1, chosen at the end of nutls_create), and nutls_set_mode(3) reports the reason kept here.
@@ -926,17 +928,16 @@ static int fused_setup(Engine* e, const WeightMap& wm) {
   if (rcz) return rcz;
   void* q = nullptr;
   // op starts + 8 phase stamps per op (wave 0) + the per-wave trace of the FZ_WTRACE build: 8 waves x ops x 12 shader-clock stamps
-  const size_t n_stamps = static_cast<size_t>(fused_plan_num_ops(v, streams)) * (9 + 8 * 12) + 1;
+  const size_t n_stamps = static_cast<size_t>(plan.num_ops) * (9 + 8 * 12) + 1;
   HIP_TRY(hipMalloc(&q, n_stamps * sizeof(unsigned long long)));
   e->allocs.push_back(q);
   HIP_TRY(hipMemset(q, 0, n_stamps * sizeof(unsigned long long)));
   e->fz_prof = static_cast<unsigned long long*>(q);
-  HIP_TRY(v == NUTLS_VARIANT_BASELINE ? fused_base_step_set_attributes()
-                                      : (streams == 4 ? fused_step_g4_set_attributes() : (streams == 2 ? fused_step_g2_set_attributes() : fused_step_set_attributes())));
+  HIP_TRY(plan.set_attributes());
   // the table for rebuilding the carried partial sums (ysum_refresh)
   std::vector<YsOp> yops;
   std::vector<float> yw;
-  if (!fused_ys_table(v, wm, &yops, &yw, &err, streams)) return fail(NUTLS_ERR_WEIGHTS, "fused plan: " + err);
+  if (!fused_ys_table(plan, wm, &yops, &yw, &err)) return fail(NUTLS_ERR_WEIGHTS, "fused plan: " + err);
   void* yo = nullptr;
   HIP_TRY(hipMalloc(&yo, yops.size() * sizeof(YsOp)));
   e->allocs.push_back(yo);
@@ -947,7 +948,7 @@ static int fused_setup(Engine* e, const WeightMap& wm) {
   if (rc) return rc;
   // the lazily written states of the one-stream plans (the packed plans hand rows over through some of them: they write everything)
   std::vector<LazyCopy> lazy;
-  if (streams == 1) fused_lazy_table(v, &lazy);
+  if (plan.streams == 1) fused_lazy_table(plan, &lazy);
   e->n_lazy = static_cast<int>(lazy.size());
   if (e->n_lazy) {
     void* lz = nullptr;
@@ -966,7 +967,7 @@ static int fused_setup(Engine* e, const WeightMap& wm) {
 static int states_materialize(Engine* e, hipStream_t s) {
   if (!e->states_stale || !e->n_lazy) { e->states_stale = false; return NUTLS_OK; }
   if (!s) HIP_TRY(hipDeviceSynchronize());      // (called from a host-side accessor: the step may have run on any stream)
-  const int block = (1 - e->next_parity) ? fused_parity_stride(e->variant) : 0;
+  const int block = (1 - e->next_parity) ? e->fz_plan->parity_stride : 0;
   HIP_TRY(launch_lazy_states(e->arena, static_cast<long long>(e->sstride), block, e->d_lazy, e->n_lazy, e->B, s));
   e->states_stale = false;
   return NUTLS_OK;
@@ -977,9 +978,9 @@ static int states_materialize(Engine* e, hipStream_t s) {
 static int ysum_refresh(Engine* e, int par, hipStream_t s) {
   if (!e->ys_dirty || !e->n_ys_ops) return NUTLS_OK;
   if (int rc = states_materialize(e, s)) return rc;      // (the sums are rebuilt from the conv-input states)
-  const int v = e->variant;
-  const int x_block = par ? 0 : fused_parity_stride(v);                       // the `prev` parity of this step
-  const int ys_block = fused_ys_off(v) + (par ? 0 : fused_ys_block(v));       // the block this step reads
+  const FusedPlan& p = *e->fz_plan;
+  const int x_block = par ? 0 : p.parity_stride;                   // the `prev` parity of this step
+  const int ys_block = p.ys_off + (par ? 0 : p.ys_block);          // the block this step reads
   HIP_TRY(launch_ysum_refresh(e->arena, static_cast<long long>(e->sstride), x_block, ys_block, e->d_ys_ops, e->d_ys_w, e->n_ys_ops, e->B, s));
   e->ys_dirty = false;
   return NUTLS_OK;
@@ -990,7 +991,7 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
   if (!e->fz_blob) return fail(NUTLS_ERR_ARG, "fused mode is not available for this handle");
   const bool base = e->variant == NUTLS_VARIANT_BASELINE;
   if (int rc = ysum_refresh(e, par, s)) return rc;
-  auto launch = base ? launch_fused_base_step : (e->fz_streams == 4 ? launch_fused_step_g4 : (e->fz_streams == 2 ? launch_fused_step_g2 : launch_fused_step));
+  auto launch = e->fz_plan->launch;
   int skew = e->fz_skew;            // (NUTLS_FUSED_SKEW at creation, nutls_debug_knob(h, "skew", v) later)
   if (e->fz_stop_at >= 0) {         // (nutls_profile_production: one-stream LSTM plan only, checked there)
     launch = launch_fused_step_stop;
@@ -1007,7 +1008,7 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
   }
   hipError_t err = launch(e->arena, static_cast<long long>(e->sstride), e->fz_blob, mag_in ? mag_in : e->io_in,
                           mag_out ? mag_out : e->io_out, e->B, par, prof ? e->fz_prof : nullptr,
-                          base ? e->d_ddb : nullptr, static_cast<int>(e->steps & 0x3fffffff), e->B / e->fz_streams, s, ta);
+                          base ? e->d_ddb : nullptr, static_cast<int>(e->steps & 0x3fffffff), e->B / e->fz_plan->streams, s, ta);
   if (err == hipErrorNotSupported && prof)
     return fail(NUTLS_ERR_ARG, "this packed fused plan has no profiling build in the library (NUTLS_BUILD_G4_PROF=1 python -m nunet_amd.build adds the 4-stream one; "
                                "NUTLS_FUSED_STREAMS=1 selects the one-stream plan)");
@@ -1199,6 +1200,7 @@ static int create_body(const void* weights, size_t n_bytes, int variant, int bat
   e->B = batch;
   e->device = device;
   e->variant = variant;
+  e->fz_plan = fused_plan(variant, 1);      // (until fused_setup chooses: what the handle-independent questions about "the plan" mean)
   e->off_bf16 = offline_frames > 0 && getenv("NUTLS_OFFLINE_FP32") == nullptr;      // (developer knob: block mode on the fp32-MFMA kernels)
   HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   int rc;
@@ -1221,7 +1223,7 @@ static int create_body(const void* weights, size_t n_bytes, int variant, int bat
   slot_reserve(e, 256 * 64, &e->t_d);
   slot_reserve(e, 256 * 128, &e->t_up);
   for (int s = 0; s < 6; ++s) slot_reserve(e, static_cast<size_t>(kDecoder[s].f0 / 2) * 128, &e->upcat[s]);
-  if (offline_frames == 0) slot_reserve(e, static_cast<size_t>(2) * fused_ys_block(variant), &e->ysum);      // (streaming handles: the fused kernel's carried partial sums)
+  if (offline_frames == 0) slot_reserve(e, static_cast<size_t>(2) * e->fz_plan->ys_block, &e->ysum);      // (streaming handles: the fused kernel's carried partial sums)
   if ((rc = arena_commit(e))) return rc;
   build_plan(e, 0);
   build_plan(e, 1);
@@ -1554,7 +1556,7 @@ int nutls_destroy(nutls_handle* h) {
 }
 
 int nutls_batch(nutls_handle* h) { return h ? h->eng.B : fail(NUTLS_ERR_ARG, "null handle"); }
-int nutls_streams_per_workgroup(nutls_handle* h) { return h ? (h->eng.fz_blob ? h->eng.fz_streams : 1) : fail(NUTLS_ERR_ARG, "null handle"); }
+int nutls_streams_per_workgroup(nutls_handle* h) { return h ? (h->eng.fz_blob ? h->eng.fz_plan->streams : 1) : fail(NUTLS_ERR_ARG, "null handle"); }
 int nutls_launches_per_step(nutls_handle* h) { return h ? static_cast<int>(h->eng.plan[0].size()) : fail(NUTLS_ERR_ARG, "null handle"); }
 
 int nutls_io_buffers(nutls_handle* h, float** mag_in, float** mag_out) {
@@ -2018,7 +2020,7 @@ int nutls_debug_trace(nutls_handle* h, int enable) {
   Engine* e = &h->eng;
   if (!enable) { e->fz_dbg = nullptr; return NUTLS_OK; }      // (the buffer stays allocated with the handle)
   if (e->offline || !e->fz_blob) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: the activation trace is the fused kernel's (streaming handle, int8 container)");
-  if (e->fz_streams != 1) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: the packed plans have no profiling build in the library (nutls_create_plan(..., 1) for the one-stream plan)");
+  if (e->fz_plan->streams != 1) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: the packed plans have no profiling build in the library (nutls_create_plan(..., 1) for the one-stream plan)");
   if (e->B > 64) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: at most 64 streams (2.5 MB of trace per stream)");
   HIP_TRY(hipSetDevice(e->device));
   if (!e->fz_dbg_buf) {
@@ -2122,11 +2124,9 @@ int nutls_profile_step(nutls_handle* h, float* ms, int n) {
   return NUTLS_OK;
 }
 
-static bool known_variant(int variant) { return variant == NUTLS_VARIANT_LSTM || variant == NUTLS_VARIANT_BASELINE; }
+int nutls_fused_num_ops(int variant) { return nutls_fused_plan_num_ops(variant, 1); }
 
-int nutls_fused_num_ops(int variant) { return known_variant(variant) ? fused_num_ops(variant) : 0; }
-
-int nutls_fused_blob_floats(int variant) { return known_variant(variant) ? fused_blob_floats(variant) : 0; }
+int nutls_fused_blob_floats(int variant) { return nutls_fused_plan_blob_floats(variant, 1); }
 
 /* Host-only (no GPU needed): the weight blob of the fused kernel for a container, for tests of the packing. */
 int nutls_fused_pack_blob(const void* weights, size_t n_bytes, int variant, float* out, size_t n_floats) {
@@ -2134,32 +2134,36 @@ int nutls_fused_pack_blob(const void* weights, size_t n_bytes, int variant, floa
 }
 
 int nutls_fused_plan_num_ops(int variant, int streams) {
-  return (known_variant(variant) && fused_has_plan(variant, streams)) ? fused_plan_num_ops(variant, streams) : 0;
+  const FusedPlan* p = fused_plan(variant, streams);
+  return p ? p->num_ops : 0;
 }
 
 int nutls_fused_plan_op_info(int variant, int streams, int index, const char** name, double* flops) {
-  if (!known_variant(variant) || !fused_has_plan(variant, streams)) return fail(NUTLS_ERR_ARG, "nutls_fused_plan_op_info: no such plan");
-  if (index < 0 || index >= fused_plan_num_ops(variant, streams)) return fail(NUTLS_ERR_ARG, "nutls_fused_plan_op_info: bad index");
-  if (name) *name = fused_plan_op_name(variant, streams, index);
-  if (flops) *flops = fused_plan_op_flops(variant, streams, index);
+  const FusedPlan* p = fused_plan(variant, streams);
+  if (!p) return fail(NUTLS_ERR_ARG, "nutls_fused_plan_op_info: no such plan");
+  if (index < 0 || index >= p->num_ops) return fail(NUTLS_ERR_ARG, "nutls_fused_plan_op_info: bad index");
+  if (name) *name = p->op_names[index];
+  if (flops) *flops = p->op_flops[index];
   return NUTLS_OK;
 }
 
 int nutls_fused_plan_blob_floats(int variant, int streams) {
-  return (known_variant(variant) && fused_has_plan(variant, streams)) ? fused_plan_blob_floats(variant, streams) : 0;
+  const FusedPlan* p = fused_plan(variant, streams);
+  return p ? p->blob_floats : 0;
 }
 
 int nutls_fused_pack_blob_plan(const void* weights, size_t n_bytes, int variant, int streams, float* out, size_t n_floats) {
   if (!weights || !out) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: null pointer");
-  if (!known_variant(variant)) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: unknown variant");
-  if (!fused_has_plan(variant, streams)) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: no plan for that many streams per workgroup");
-  if (n_floats != static_cast<size_t>(fused_plan_blob_floats(variant, streams))) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: n_floats must equal nutls_fused_blob_floats()");
+  if (!fused_plan(variant, 1)) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: unknown variant");
+  const FusedPlan* p = fused_plan(variant, streams);
+  if (!p) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: no plan for that many streams per workgroup");
+  if (n_floats != static_cast<size_t>(p->blob_floats)) return fail(NUTLS_ERR_ARG, "nutls_fused_pack_blob: n_floats must equal nutls_fused_blob_floats()");
   WeightMap wm;
   std::string err;
   std::vector<float> blob;
   try {
     if (!parse_weight_blob(weights, n_bytes, &wm, &err)) return fail(NUTLS_ERR_WEIGHTS, err);
-    if (fused_pack_blob(variant, wm, &blob, &err, streams) != FZ_PACK_OK) return fail(NUTLS_ERR_WEIGHTS, err);
+    if (fused_pack_blob(*p, wm, &blob, &err) != FZ_PACK_OK) return fail(NUTLS_ERR_WEIGHTS, err);
   } catch (const std::exception& ex) {
     return fail(NUTLS_ERR_WEIGHTS, std::string("weight container: ") + ex.what());
   }
@@ -2168,20 +2172,21 @@ int nutls_fused_pack_blob_plan(const void* weights, size_t n_bytes, int variant,
 }
 
 int nutls_fused_op_info(int variant, int index, const char** name, double* flops) {
-  if (!known_variant(variant)) return fail(NUTLS_ERR_ARG, "nutls_fused_op_info: unknown variant");
-  if (index < 0 || index >= fused_num_ops(variant)) return fail(NUTLS_ERR_ARG, "nutls_fused_op_info: bad index");
-  if (name) *name = fused_op_name(variant, index);
-  if (flops) *flops = fused_op_flops(variant, index);
+  const FusedPlan* p = fused_plan(variant, 1);
+  if (!p) return fail(NUTLS_ERR_ARG, "nutls_fused_op_info: unknown variant");
+  if (index < 0 || index >= p->num_ops) return fail(NUTLS_ERR_ARG, "nutls_fused_op_info: bad index");
+  if (name) *name = p->op_names[index];
+  if (flops) *flops = p->op_flops[index];
   return NUTLS_OK;
 }
 
 int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, int steps) {
   if (!h || !cum_us) return fail(NUTLS_ERR_ARG, "nutls_profile_production: null pointer");
   Engine* e = &h->eng;
-  if (e->offline || e->mode != 3 || !e->fz_blob || e->variant != NUTLS_VARIANT_LSTM || e->fz_streams != 1 || e->ctfa_causal)
+  if (e->offline || e->mode != 3 || !e->fz_blob || e->variant != NUTLS_VARIANT_LSTM || e->fz_plan->streams != 1 || e->ctfa_causal)
     return fail(NUTLS_ERR_ARG, "nutls_profile_production: a streaming handle of the LSTM variant in the fused mode on the one-stream plan, per-frame CTFA "
                                "(the stop twin exists for that kernel only)");
-  const int nops = fused_plan_num_ops(e->variant, 1);
+  const int nops = e->fz_plan->num_ops;
   if (n != nops + 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: n must equal nutls_fused_num_ops(variant) + 1");
   if (reps < 1 || steps < 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: reps and steps must be positive");
   HIP_TRY(hipSetDevice(e->device));
@@ -2222,7 +2227,7 @@ int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, i
 int nutls_profile_fused(nutls_handle* h, double* us, int n) {
   if (!h || !us) return fail(NUTLS_ERR_ARG, "nutls_profile_fused: null pointer");
   Engine* e = &h->eng;
-  if (n != fused_plan_num_ops(e->variant, e->fz_streams))
+  if (n != e->fz_plan->num_ops)
     return fail(NUTLS_ERR_ARG, "nutls_profile_fused: n must equal nutls_fused_plan_num_ops(variant, nutls_streams_per_workgroup(h))");
   HIP_TRY(hipSetDevice(e->device));
   const int par = e->next_parity;
@@ -2250,14 +2255,14 @@ int nutls_profile_fused(nutls_handle* h, double* us, int n) {
     HIP_TRY(hipMemcpy(sub.data(), e->fz_prof + n + 1, sub.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (FILE* f = fopen(dump, "w")) {
       for (int i = 0; i < n; ++i) {
-        fprintf(f, "%-24s total %6.2f |", fused_plan_op_name(e->variant, e->fz_streams, i), us[i]);
+        fprintf(f, "%-24s total %6.2f |", e->fz_plan->op_names[i], us[i]);
         // stamp slots in chronological order: 0 loads issued, 5 carried weights arrived, 6 MFMA loop done (4x4 path),
         // 1 partials / parameters written, 2 past barrier 1, 3 epilogue done, 4 next image built
         const int order[7] = {0, 5, 6, 1, 2, 3, 4};
         const char* nm_conv[7] = {"issue", "wwait", "mloop", "mfma", "bar1", "epi", "build"};
         // CTFA ops: loads issued | column sums | barrier | time-attention perceptron | frequency-attention perceptron + gate | barrier; the rest (bar2) = gate applied
         const char* nm_ctfa[7] = {"issue", "colsum", "-", "bar1", "mlp_ta", "mlp_fa", "barg"};
-        const char* opn = fused_plan_op_name(e->variant, e->fz_streams, i);
+        const char* opn = e->fz_plan->op_names[i];
         const size_t ol = std::strlen(opn);
         const char* const* nm = (ol >= 4 && std::strcmp(opn + ol - 4, "ctfa") == 0) ? nm_ctfa : nm_conv;
         unsigned long long prev = t[i];

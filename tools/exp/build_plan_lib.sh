@@ -20,9 +20,10 @@ TUS=${EXP_TUS:-"fused_step fused_step_prof"}
 for f in $TUS; do $CC -c $S/$f.hip -o $S/$f.o & done
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -c $S/fused_host.cpp -o $S/fused_host.o &
 wait
-OBJS="$S/fused_host.o"
-for s in fused_step fused_step_prof fused_step_stop fused_step_g2 fused_step_g4 fused_base fused_base_prof kernels stft offline weights engine; do
-  case " $TUS " in *" $s "*) OBJS="$OBJS $S/$s.o";; *) OBJS="$OBJS $P/build/$s.o";; esac
+# (the objects of the library: the build's own list)
+OBJS=""
+for s in $(cd $R && python -c "import os, nunet_amd.build as b; print(' '.join(os.path.splitext(s)[0] for s in b.SOURCES))"); do
+  case " $TUS fused_host " in *" $s "*) OBJS="$OBJS $S/$s.o";; *) OBJS="$OBJS $P/build/$s.o";; esac
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $P/build/exp/libnutls_$NAME.so $OBJS
 rm -rf $S
