@@ -85,6 +85,41 @@ int nutls_step(nutls_handle* h, const float* mag_in, float* mag_out, void* strea
  * copies at all: the kernel reads the frame from and writes the result to the pinned host buffers over the link (PCIe) itself. */
 int nutls_step_host(nutls_handle* h, const float* mag_in, float* mag_out);
 
+/* ---- Per-stream active mask: step a chosen subset of the handle's streams ------------------------------------
+ * The B streams of a handle are independent, and so is their time: a server that multiplexes calls onto one handle has slots whose
+ * frame has not arrived at a tick (clock drift, jitter, a call that has not joined yet).  `active` is [B] bytes, one per stream:
+ * nonzero = the stream takes this frame, zero = the stream is HELD.  A held stream, in one call:
+ *   - keeps everything of it that survives the call exactly as it was: the 130 signature states as every accessor shows them, the
+ *     carried partial sums of the two-tap convs, and (nutls_enhance_hop_active) its previous hop and overlap tail;
+ *   - its row of mag_in / pcm_in has no effect (it may hold anything, NaN included).  It is not even read where the stream's whole
+ *     workgroup is held -- always on the one-stream plan; on a packed plan a workgroup with held AND active slots runs the step for all
+ *     of them, so the row is read and computed on there, and the results are then replaced by the held state and the zero row;
+ *   - its row of mag_out / pcm_out is written with ZEROS (deterministic: never stale data, never the input).
+ * A stream that takes frames x0, x1, x2 at ticks 0, 3 and 4 produces the same bits -- outputs and states -- as one that took them at
+ * ticks 0, 1 and 2; a held tick costs it nothing but time.  The other streams are not affected in any bit.  A new call joins a slot with
+ * nutls_reset(h, b).  (The handle-wide state parity still flips on every call: a held stream's state is copied across, which is
+ * why holding is not free -- about 1.9 MB of device traffic per held stream and call -- but it needs no weights and no arithmetic.)
+ *
+ * nutls_step_active / nutls_enhance_hop_active: `active` is a DEVICE pointer, read by the kernels: it must stay valid and unmodified
+ * until the work queued on `stream` has run.  The _host entries take `active` in HOST memory (pageable or pinned) and copy the B bytes
+ * themselves; with buffers from nutls_host_alloc nutls_step_host_active still runs without copies of the frames.
+ * active == NULL means all streams: the call IS the entry without the mask (same code path, same bits).
+ *
+ * After nutls_state_set the masked launches write all 130 states of the active streams themselves (normally 40 conv-input states are left
+ * to be rebuilt on demand, see nutls_state_get) until every stream has taken a frame since the edit -- the _host entries see the masks and
+ * follow that; with DEVICE masks the library cannot, and the more expensive launches last until one call steps all streams (NULL mask).
+ *
+ * Supported: streaming handles of the LSTM variant in the fused mode (mode 3) with NUTLS_CTFA_FRAME, on every plan (1, 2 or 4 streams
+ * per workgroup).  With a non-NULL mask everything else returns NUTLS_ERR_ARG (reason in nutls_last_error) and changes nothing -- never
+ * a silent step of all streams:
+ *   - modes 0 / 1: the per-layer plans and the captured graphs are handle-wide;
+ *   - the baseline variant: its dilated-dense history rings are updated in place, at a slot derived from the handle's frame counter
+ *     -- holding a stream there needs a ring position per stream;
+ *   - NUTLS_CTFA_CAUSAL32 on a streaming handle: the same, for the time-attention ring;
+ *   - offline handles (they step blocks of frames of one utterance each: nutls_process_block). */
+int nutls_step_active(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active, void* stream);
+int nutls_step_host_active(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active);
+
 /* Page-locked, device-visible host memory for the buffers handed to nutls_step_host / nutls_enhance_hop_host / nutls_process_block_host
  * (what TF-Lite's interpreter.tensor(i) zero-copy view is to set_tensor / get_tensor in the reference's loop, interpreter_proposed.py:215-350:
  * the caller produces its frames in, and consumes its results from, memory the device can reach).  NULL on failure (nutls_last_error).
@@ -107,6 +142,11 @@ void nutls_host_free(void* p);
 int nutls_enhance_hop(nutls_handle* h, const float* pcm_in, float* pcm_out, int dc_mode, void* stream);
 /* Same with HOST buffers (H2D, pipeline, D2H, synchronises). */
 int nutls_enhance_hop_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int dc_mode);
+/* The same with a per-stream active mask (see nutls_step_active: `active` a DEVICE pointer here, HOST memory in the _host entry; NULL =
+ * nutls_enhance_hop): analysis, model step and synthesis all skip the held streams -- previous hop, overlap tail and model state stay
+ * as they are, the held rows of pcm_out are zero hops.  Each stream's concatenated active hops equal what a handle fed in lockstep returns. */
+int nutls_enhance_hop_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream);
+int nutls_enhance_hop_host_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode);
 /* The two halves on their own (testing, custom models): analysis of one hop into the library's mag_in buffer
  * (+ phase kept inside), synthesis of one hop from the library's mag_out buffer.  Device pointers. */
 int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream);

@@ -174,6 +174,10 @@ struct Engine {
   float *fz_ta_zero = nullptr, *fz_ta_ring = nullptr, *fz_ta_sum = nullptr;
   float* fz_dbg_buf = nullptr;
   int fz_stop_at = -1;         // >= 0: fused launches run the stop twin and end in front of this op (nutls_profile_production)
+  unsigned char* d_active = nullptr;     // [B] bytes: device copy of the mask of the _host entries of nutls_step_active / nutls_enhance_hop_active
+  bool lazy_edited = false;    // nutls_state_set wrote a lazily written state and not every stream has stepped since: masked steps then write every state
+                               // (a held stream's edited row must not be rebuilt from its older second copy: run_fused)
+  std::vector<unsigned char> lazy_pending;   // while lazy_edited: per stream, 1 = has not stepped since the edit (followed through the HOST masks: note_active)
   int fz_skew = 0;             // FzTa::skew of the fused launches (start skew of the workgroups; experiment builds of the kernel: see nutls_debug_knob)
   float* fz_dbg = nullptr;     // activation trace [B][kDbgSlots][kDbgSlotFloats] (nutls_debug_trace): steps then run on the profiling build, which fills it
   std::string fz_reason;                 // why there is none (what the packer said), for nutls_set_mode(3)
@@ -987,7 +991,9 @@ static int ysum_refresh(Engine* e, int par, hipStream_t s) {
 }
 
 // (mag_in / mag_out: the caller's device buffers, read by the input layer and written by the last op directly -- no staging copies)
-static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* mag_in = nullptr, float* mag_out = nullptr) {
+// (active: device mask of nutls_step_active, null = every stream takes the frame)
+static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* mag_in = nullptr, float* mag_out = nullptr,
+                     const unsigned char* active = nullptr) {
   if (!e->fz_blob) return fail(NUTLS_ERR_ARG, "fused mode is not available for this handle");
   const bool base = e->variant == NUTLS_VARIANT_BASELINE;
   if (int rc = ysum_refresh(e, par, s)) return rc;
@@ -997,7 +1003,14 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
     launch = launch_fused_step_stop;
     skew = e->fz_stop_at;
   }
-  const int eager = (e->eager_states || !e->n_lazy) ? 1 : 0;
+  int eager = (e->eager_states || !e->n_lazy) ? 1 : 0;
+  if (active && e->lazy_edited && !eager) {
+    // A held stream keeps the rows nutls_state_set gave it, and states_materialize would rebuild its lazily written states from second copies
+    // that may be older than the edit.  Until a step of all streams has replaced every edited row, masked launches write every state
+    // themselves: nothing is left for states_materialize to rebuild (nutls_state_set left the `prev` side complete).
+    if (int rc = states_materialize(e, s)) return rc;
+    eager = 1;
+  }
   float* const dbg = prof ? e->fz_dbg : nullptr;      // (activation trace: the profiling builds only)
   const long long dbg_ss = static_cast<long long>(kDbgSlots) * kDbgSlotFloats;
   FzTa ta{e->fz_ta_zero, e->fz_ta_zero + 64, 0, 0, 0, 0, skew, eager, dbg, dbg_ss};
@@ -1006,6 +1019,7 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
     HIP_TRY(launch_ta_sum(e->fz_ta_ring, e->fz_ta_sum, slot, e->B, s));
     ta = FzTa{e->fz_ta_sum, e->fz_ta_ring + slot * 64, 12 * 64, 64, 12 * 32 * 64, 32 * 64, skew, eager, dbg, dbg_ss};
   }
+  ta.active = active;
   hipError_t err = launch(e->arena, static_cast<long long>(e->sstride), e->fz_blob, mag_in ? mag_in : e->io_in,
                           mag_out ? mag_out : e->io_out, e->B, par, prof ? e->fz_prof : nullptr,
                           base ? e->d_ddb : nullptr, static_cast<int>(e->steps & 0x3fffffff), e->B / e->fz_plan->streams, s, ta);
@@ -1015,6 +1029,7 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
   if (err != hipSuccess) return fail(NUTLS_ERR_HIP, std::string("fused step launch: ") + hipGetErrorString(err));
   if (base) e->d_step_stale = true;      // ring position of the dilated-dense history went in by value: one launch per step
   e->states_stale = !eager;              // (materialised on demand: states_materialize)
+  if (!active) e->lazy_edited = false;   // (every stream stepped: every edited row has been consumed and replaced; masked steps: note_active)
   return NUTLS_OK;
 }
 
@@ -1601,8 +1616,37 @@ int nutls_set_mode(nutls_handle* h, int mode) {
   return NUTLS_OK;
 }
 
+// Where a per-stream active mask is supported: streaming handles of the LSTM variant on the fused kernel with the frame-mode CTFA.  Everything
+// else keeps per-stream time in places a mask cannot reach (nutls.h, nutls_step_active) and refuses -- never a silent full step.
+static int check_active(const Engine* e, const char* who) {
+  const std::string w = std::string(who) + ": a per-stream active mask ";
+  if (e->offline) return fail(NUTLS_ERR_ARG, w + "needs a streaming handle (an offline handle steps whole blocks: nutls_process_block)");
+  if (e->variant != NUTLS_VARIANT_LSTM)
+    return fail(NUTLS_ERR_ARG, w + "is not supported for the baseline variant: its dilated-dense history rings are updated in place at a slot derived from the handle's frame counter");
+  if (e->ctfa_causal)
+    return fail(NUTLS_ERR_ARG, w + "is not supported with NUTLS_CTFA_CAUSAL32: the time-attention ring is addressed by the handle's frame counter -- nutls_set_ctfa_mode(NUTLS_CTFA_FRAME) first");
+  if (e->mode != 3 || !e->fz_blob)
+    return fail(NUTLS_ERR_ARG, w + "needs the fused kernel (mode 3): the per-layer plans and captured graphs of modes 0 / 1 are handle-wide");
+  if (e->fz_stop_at >= 0) return fail(NUTLS_ERR_ARG, w + "cannot be combined with nutls_profile_production");
+  return NUTLS_OK;
+}
+
+static int step_impl(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active, void* stream);
+
 int nutls_step(nutls_handle* h, const float* mag_in, float* mag_out, void* stream) {
   if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_step: null pointer");
+  return step_impl(h, mag_in, mag_out, nullptr, stream);
+}
+
+int nutls_step_active(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active, void* stream) {
+  if (!active) return nutls_step(h, mag_in, mag_out, stream);
+  if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_step_active: null pointer");
+  if (int rc = check_active(&h->eng, "nutls_step_active")) return rc;
+  return step_impl(h, mag_in, mag_out, active, stream);
+}
+
+// (active non-null: checked by the caller, fused mode)
+static int step_impl(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active, void* stream) {
   Engine* e = &h->eng;
   if (e->offline) return fail(NUTLS_ERR_ARG, "nutls_step: offline handle, use nutls_process_block");
   HIP_TRY(hipSetDevice(e->device));
@@ -1614,7 +1658,7 @@ int nutls_step(nutls_handle* h, const float* mag_in, float* mag_out, void* strea
   if (e->mode != 3)
     if (int rc = states_materialize(e, s)) return rc;      // (the per-layer kernels read every conv-input state)
   if (e->mode == 3) {
-    int rc = run_fused(e, par, s, e->fz_dbg != nullptr, mag_in, mag_out);
+    int rc = run_fused(e, par, s, e->fz_dbg != nullptr, mag_in, mag_out, active);
     if (rc) return rc;
   } else if (e->mode == 1) {
     e->ys_dirty = true;
@@ -1666,67 +1710,164 @@ static bool host_pinned(const void* p, size_t bytes) {
   return static_cast<const char*>(p) + bytes <= it->first + it->second;
 }
 
+// The B mask bytes of a _host entry, copied to the handle's device buffer on the library's stream (in front of the work that reads them).
+static int upload_active(Engine* e, const unsigned char* active) {
+  if (!e->d_active) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, static_cast<size_t>(e->B)));
+    e->allocs.push_back(p);
+    e->d_active = static_cast<unsigned char*>(p);
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_active, active, static_cast<size_t>(e->B), hipMemcpyHostToDevice, e->stream));
+  return NUTLS_OK;
+}
+
+// After a masked step whose mask the host has seen (the _host entries): the streams that took the frame have replaced every row
+// nutls_state_set gave them; once all have, masked launches go back to leaving the lazily written states to states_materialize.
+// (A device mask is not visible here: with those, eager launches last until a step of all streams -- nutls.h, nutls_step_active.)
+static void note_active(Engine* e, const unsigned char* active) {
+  if (!e->lazy_edited) return;
+  bool pending = false;
+  for (int b = 0; b < e->B; ++b) {
+    if (active[b]) e->lazy_pending[b] = 0;
+    pending = pending || e->lazy_pending[b];
+  }
+  if (!pending) e->lazy_edited = false;
+}
+
+static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active);
+
 int nutls_step_host(nutls_handle* h, const float* mag_in, float* mag_out) {
   if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_step_host: null pointer");
+  return step_host_impl(h, mag_in, mag_out, nullptr);
+}
+
+int nutls_step_host_active(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active) {
+  if (!active) return nutls_step_host(h, mag_in, mag_out);
+  if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_step_host_active: null pointer");
+  if (int rc = check_active(&h->eng, "nutls_step_host_active")) return rc;
+  return step_host_impl(h, mag_in, mag_out, active);
+}
+
+// (active: HOST mask or null; checked by the caller)
+static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active) {
   Engine* e = &h->eng;
   HIP_TRY(hipSetDevice(e->device));
   const size_t bytes = static_cast<size_t>(e->B) * NUTLS_BINS * sizeof(float);
+  const unsigned char* d_act = nullptr;
+  if (active) {
+    if (int rc = upload_active(e, active)) return rc;
+    d_act = e->d_active;
+  }
   if (e->mode == 3 && host_pinned(mag_in, bytes) && host_pinned(mag_out, bytes)) {
     // the fused kernel takes the caller's buffers as they are: the frame crosses the link inside the launch, no copy commands
     // (B = 1024: 0.976 ms per call against 1.048 through two DMA copies of the same pinned buffers and 1.10-1.11 from pageable memory)
-    int rc = nutls_step(h, mag_in, mag_out, e->stream);
+    int rc = step_impl(h, mag_in, mag_out, d_act, e->stream);
     if (rc) return rc;
+    if (active) note_active(e, active);
     HIP_TRY(hipStreamSynchronize(e->stream));
     return NUTLS_OK;
   }
   HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyHostToDevice, e->stream));
-  int rc = nutls_step(h, e->io_in, e->io_out, e->stream);
+  int rc = step_impl(h, e->io_in, e->io_out, d_act, e->stream);
   if (rc) return rc;
+  if (active) note_active(e, active);
   HIP_TRY(hipMemcpyAsync(mag_out, e->io_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return NUTLS_OK;
 }
 
-int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream) {
-  if (!h || !pcm_in) return fail(NUTLS_ERR_ARG, "nutls_stft_hop: null pointer");
+// (active: device mask or null -- a held stream's previous hop, magnitudes and phasors stay as they are)
+static int stft_hop_impl(nutls_handle* h, const float* pcm_in, const unsigned char* active, void* stream) {
   Engine* e = &h->eng;
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
-  HIP_TRY(launch_stft_hop(pcm_in, e->fe_tail, e->fe_win, e->fe_tw, e->io_in, e->fe_ph, e->B, static_cast<hipStream_t>(stream)));
+  HIP_TRY(launch_stft_hop(pcm_in, e->fe_tail, e->fe_win, e->fe_tw, e->io_in, e->fe_ph, e->B, static_cast<hipStream_t>(stream), active));
   return NUTLS_OK;
 }
 
+int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream) {
+  if (!h || !pcm_in) return fail(NUTLS_ERR_ARG, "nutls_stft_hop: null pointer");
+  return stft_hop_impl(h, pcm_in, nullptr, stream);
+}
+
+static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const unsigned char* active, void* stream);
+
 int nutls_istft_hop(nutls_handle* h, float* pcm_out, int dc_mode, void* stream) {
   if (!h || !pcm_out) return fail(NUTLS_ERR_ARG, "nutls_istft_hop: null pointer");
+  return istft_hop_impl(h, pcm_out, dc_mode, nullptr, stream);
+}
+
+// (active: device mask or null -- a held stream gets a zero hop, its overlap tail stays as it is)
+static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const unsigned char* active, void* stream) {
   if (dc_mode != NUTLS_DC_EDGE && dc_mode != NUTLS_DC_ZERO) return fail(NUTLS_ERR_ARG, "dc_mode must be NUTLS_DC_EDGE or NUTLS_DC_ZERO");
   Engine* e = &h->eng;
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
   HIP_TRY(launch_istft_hop(e->io_out, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->B,
-                           static_cast<hipStream_t>(stream)));
+                           static_cast<hipStream_t>(stream), active));
   return NUTLS_OK;
+}
+
+// analysis -> model step on the library buffers -> synthesis, all three with the (device) mask or without one
+static int enhance_hop_impl(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  int rc = stft_hop_impl(h, pcm_in, active, stream);
+  if (rc) return rc;
+  Engine* e = &h->eng;
+  if ((rc = step_impl(h, e->io_in, e->io_out, active, stream))) return rc;
+  return istft_hop_impl(h, pcm_out, dc_mode, active, stream);
 }
 
 int nutls_enhance_hop(nutls_handle* h, const float* pcm_in, float* pcm_out, int dc_mode, void* stream) {
   if (!h || !pcm_in || !pcm_out) return fail(NUTLS_ERR_ARG, "nutls_enhance_hop: null pointer");
-  int rc = nutls_stft_hop(h, pcm_in, stream);
-  if (rc) return rc;
-  Engine* e = &h->eng;
-  if ((rc = nutls_step(h, e->io_in, e->io_out, stream))) return rc;
-  return nutls_istft_hop(h, pcm_out, dc_mode, stream);
+  return enhance_hop_impl(h, pcm_in, pcm_out, nullptr, dc_mode, stream);
 }
+
+// (refusals come before the analysis: a refused call leaves the previous hops where they were)
+static int check_enhance_active(nutls_handle* h, int dc_mode, const char* who) {
+  if (int rc = check_active(&h->eng, who)) return rc;
+  if (dc_mode != NUTLS_DC_EDGE && dc_mode != NUTLS_DC_ZERO) return fail(NUTLS_ERR_ARG, "dc_mode must be NUTLS_DC_EDGE or NUTLS_DC_ZERO");
+  return NUTLS_OK;
+}
+
+int nutls_enhance_hop_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  if (!active) return nutls_enhance_hop(h, pcm_in, pcm_out, dc_mode, stream);
+  if (!h || !pcm_in || !pcm_out) return fail(NUTLS_ERR_ARG, "nutls_enhance_hop_active: null pointer");
+  if (int rc = check_enhance_active(h, dc_mode, "nutls_enhance_hop_active")) return rc;
+  return enhance_hop_impl(h, pcm_in, pcm_out, active, dc_mode, stream);
+}
+
+static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode);
 
 int nutls_enhance_hop_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int dc_mode) {
   if (!h || !pcm_in || !pcm_out) return fail(NUTLS_ERR_ARG, "nutls_enhance_hop_host: null pointer");
+  return enhance_hop_host_impl(h, pcm_in, pcm_out, nullptr, dc_mode);
+}
+
+int nutls_enhance_hop_host_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode) {
+  if (!active) return nutls_enhance_hop_host(h, pcm_in, pcm_out, dc_mode);
+  if (!h || !pcm_in || !pcm_out) return fail(NUTLS_ERR_ARG, "nutls_enhance_hop_host_active: null pointer");
+  if (int rc = check_enhance_active(h, dc_mode, "nutls_enhance_hop_host_active")) return rc;
+  return enhance_hop_host_impl(h, pcm_in, pcm_out, active, dc_mode);
+}
+
+// (active: HOST mask or null; checked by the caller)
+static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode) {
   Engine* e = &h->eng;
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
   const size_t bytes = static_cast<size_t>(e->B) * NUTLS_FRAME_STEP * sizeof(float);
+  const unsigned char* d_act = nullptr;
+  if (active) {
+    if ((rc = upload_active(e, active))) return rc;
+    d_act = e->d_active;
+  }
   HIP_TRY(hipMemcpyAsync(e->fe_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
-  if ((rc = nutls_enhance_hop(h, e->fe_pcm_in, e->fe_pcm_out, dc_mode, e->stream))) return rc;
+  if ((rc = enhance_hop_impl(h, e->fe_pcm_in, e->fe_pcm_out, d_act, dc_mode, e->stream))) return rc;
+  if (active) note_active(e, active);
   HIP_TRY(hipMemcpyAsync(pcm_out, e->fe_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return NUTLS_OK;
@@ -1849,6 +1990,8 @@ int nutls_state_set(nutls_handle* h, const char* name, const float* host_buf, si
     return NUTLS_OK;
   }
   e->ys_dirty = true;      // a conv-input state changed under the fused kernel's carried partial sums: rebuilt before its next step
+  e->lazy_edited = e->n_lazy != 0;
+  if (e->lazy_edited) e->lazy_pending.assign(static_cast<size_t>(e->B), 1);
   // (causal32 CTFA: the 31-frame time-attention history of a streaming handle is library state outside the ABI's tensors.  It is NOT touched
   //  here: nutls_state_set takes [B, ...] buffers, and the per-stream workflow -- get, change one stream's row, set -- must leave the other
   //  B - 1 live streams alone.  A caller that loads a new utterance into stream b calls nutls_reset(h, b) first: nutls.h, nutls_state_set.)

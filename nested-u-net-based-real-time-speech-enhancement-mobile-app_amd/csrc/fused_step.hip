@@ -1599,6 +1599,59 @@ struct FzArgs {
   FzTa ta;                   // CTFA frequency branch: see nutls_internal.hpp
 };
 
+// ---- held streams (FzTa::active; nutls_step_active) --------------------------------------------------------------------------------------
+// A stream whose byte of the mask is 0 does not take this frame, but the handle's state parity flips for everybody: its `cur` parity block
+// becomes an exact copy of its `prev` block, the block of carried sums the step would have written (ysw) a copy of the one it read (ysr), and
+// its output row is zeroed.  The WHOLE parity block is copied, not the live state tensors only: the lazily written conv-input states and
+// their second copies (the skip-connection slices) live there too and must stay consistent with each other.  Every one of these rows is read
+// next by a LATER launch only -- the cache-policy argument at the top of this file: non-temporal loads and stores, so that a held stream's
+// 1.9 MB (2 x (206 208 + 31 360) floats) do not evict the weights the active workgroups share in L2.  Everything is addressed from the kernel arguments (scalar reloads),
+// not from Ctx: nothing of the step's register budget is kept alive for it.
+// bit g set: stream slot g of the workgroup takes this frame (uniform: every lane reads the same NSTREAMS bytes)
+__device__ __forceinline__ unsigned active_bits(const unsigned char* active, int stream) {
+  unsigned m = 0;
+#pragma unroll
+  for (int g = 0; g < NSTREAMS; ++g) m |= (active[stream + g] != 0 ? 1u : 0u) << g;
+  return __builtin_amdgcn_readfirstlane(m);
+}
+template <unsigned BYTES>
+__device__ __forceinline__ void hold_copy(gcb_t src, gcb_t dst, int tid) {
+  static_assert(BYTES % 16 == 0, "the held blocks are copied as 16-byte vectors");
+  constexpr unsigned STEP = THREADS * 16, U = 8;      // 8 vectors per thread in flight
+  unsigned o = static_cast<unsigned>(tid) * 16;
+  for (; o + (U - 1) * STEP < BYTES; o += U * STEP) {
+    f32x4 v[U];
+#pragma unroll
+    for (unsigned k = 0; k < U; ++k) v[k] = ld_once(src, o + k * STEP);
+#pragma unroll
+    for (unsigned k = 0; k < U; ++k) st_next(dst, o + k * STEP, v[k]);
+  }
+  for (; o < BYTES; o += STEP) st_next(dst, o, ld_once(src, o));
+}
+__device__ __forceinline__ void hold_stream(const float* arena, long long sstride, float* io_out, int par, int stream, int tid) {
+  const float* slice = arena + static_cast<size_t>(stream) * sstride;
+  hold_copy<kParityStride * 4u>((gcb_t)(unsigned long long)(slice + (par ? 0 : kParityStride)),
+                                (gcb_t)(unsigned long long)(slice + (par ? kParityStride : 0)), tid);
+  hold_copy<kYsBlock * 4u>((gcb_t)(unsigned long long)(slice + kYsOff + (par ? 0 : kYsBlock)),
+                           (gcb_t)(unsigned long long)(slice + kYsOff + (par ? kYsBlock : 0)), tid);
+  if (tid < 256) io_out[static_cast<size_t>(stream) * 256 + tid] = 0.f;
+}
+
+// A thread index for the hold path behind the step that owes nothing to the step's registers: every wave draws a ticket 0 .. 7 from an LDS
+// counter (the step is over, LDS is free), thread = 64 ticket + lane.  Any one-to-one assignment of the 512 threads serves a copy; reading
+// threadIdx.x there instead keeps its register alive across all 154 ops, and the two-stream kernel, one register below the file's limit,
+// then spills.  (Call behind a workgroup barrier; ends with the counter at 8.)
+__device__ __forceinline__ int ticket_tid() {
+  unsigned* const ctr = reinterpret_cast<unsigned*>(lds);
+  *ctr = 0u;
+  lds_barrier();
+  const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  unsigned w = 0;
+  if (lane == 0) w = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  w = __builtin_amdgcn_readfirstlane(w);
+  return static_cast<int>(w * 64u + lane);
+}
+
 #if FZ_STREAMS == 2
 #define FZ_KERNEL nutls_fused_step_g2_kernel
 #define FZ_LAUNCH launch_fused_step_g2
@@ -1642,6 +1695,8 @@ struct FzArgs {
 #define FZ_LAUNCH_PROF launch_fused_step_prof
 #define FZ_ATTR_PROF fused_step_prof_set_attributes
 #endif
+// (FzArgs must stay the kernel's ONLY parameter: the hold path behind the step of the packed builds re-reads it from offset 0 of the
+//  kernel-argument segment -- see there.  A second parameter goes INTO FzArgs.)
 __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
   constexpr bool PROF = FZ_PROF != 0;
   // One workgroup per stream, grid = B (the hardware queues the workgroups that do not fit).  No loop over streams here:
@@ -1702,6 +1757,15 @@ __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
     const int n = (blockIdx.x & 3) * a.ta.skew;
     for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
   }
+  // Per-stream active mask (null = everybody steps: one scalar test here, one behind the last op, nothing per op).  A workgroup none of
+  // whose streams takes the frame holds them all and ends before the first weight is fetched.
+  if (a.ta.active) {
+    if (active_bits(a.ta.active, stream) == 0u) {
+#pragma unroll
+      for (int g = 0; g < NSTREAMS; ++g) hold_stream(a.arena, a.sstride, a.io_out, a.par, stream + g, threadIdx.x);
+      return;
+    }
+  }
   Carry<0> c0;
   {
     int tid = threadIdx.x;
@@ -1709,6 +1773,27 @@ __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
     prefetch_y<1>(cx, tid, c0.yp2);
   }
   run_from<0, PROF>(cx, c0);
+  if constexpr (NSTREAMS > 1) {
+    // A packed group with held AND active slots ran the step for all of them (the packed ops need no masked variants); once every
+    // store of the step has landed, the hold path overwrites what it wrote for the held slots.
+    // (The arguments are re-read from the kernel-argument segment through a pointer the compiler cannot see through -- FzArgs is the kernel's
+    //  only parameter, at offset 0 -- and the thread index is a ticket: nothing the step computed, not even threadIdx.x or an argument
+    //  register, is kept alive across the 154 ops for the sake of this path.  With `a` and threadIdx.x here the two-stream kernel, one
+    //  register below the limit, spilled one.)
+    if (a.ta.active) {
+      const FzArgs* ka = (const FzArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ka));
+      const int strm = __builtin_amdgcn_workgroup_id_x() * NSTREAMS;
+      const unsigned act = active_bits(ka->ta.active, strm);
+      if (act != (1u << NSTREAMS) - 1u) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const int t = ticket_tid();
+#pragma unroll
+        for (int g = 0; g < NSTREAMS; ++g)
+          if (!((act >> g) & 1u)) hold_stream(ka->arena, ka->sstride, ka->io_out, ka->par, strm + g, t);
+      }
+    }
+  }
   if (PROF && cx.prof && threadIdx.x == 0) cx.prof[kNumOps] = wall_clock64();
 }
 

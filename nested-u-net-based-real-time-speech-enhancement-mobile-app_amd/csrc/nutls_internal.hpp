@@ -199,9 +199,12 @@ constexpr int NUTLS_DEV_BINS = 256;
 constexpr int NUTLS_FRAME_LEN = 512;    // interpreter_proposed.py:17
 constexpr int NUTLS_FRAME_STEP = 256;   // interpreter_proposed.py:18
 // STFT front end / inverse-STFT + overlap-add back end of the streaming loop (stft.hip)
-hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s);
+// `active`: per-stream mask of nutls_enhance_hop_active ([B] bytes on the device, null = everybody).  A held stream's workgroup leaves the
+// previous hop / the overlap tail untouched; the analysis writes nothing for it, the synthesis a zero hop.
+hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s,
+                           const unsigned char* active = nullptr);
 hipError_t launch_istft_hop(const float* est, const float* ph, const float* inv_win, const float* tw, float* ola, float* pcm_out,
-                            int dc_edge, int B, hipStream_t s);
+                            int dc_edge, int B, hipStream_t s, const unsigned char* active = nullptr);
 // Waveform block mode of the offline handles (stft_block.hip): the same analysis / synthesis for n_hops consecutive hops of each of U
 // utterances in one launch.  pcm / pcm_out [U][n_hops * 256]; mag / est [U][n_hops][256]; ph [U][n_hops][257] float2.  The carried previous hop
 // (tail) and overlap tail (ola), [U][256], are read from *_in and written to *_out: two buffers each, since the first tile of an utterance reads
@@ -245,6 +248,10 @@ struct FzTa {
   //  12 CTFA outputs, the 6 up-sampling outputs) are copied to `dbg` + stream * dbg_sstride + slot * kDbgSlotFloats; null = off.  The
   //  production kernels do not look at these fields.)
   float* dbg; long long dbg_sstride;
+  // (and: the per-stream active mask of nutls_step_active, [B] bytes on the device, null = every stream takes the frame.  A stream whose
+  //  byte is 0 is HELD: the kernel copies its `prev` parity block and carried sums onto the `cur` side and zeroes its output row --
+  //  fused_step.hip hold_stream.  LSTM variant, frame-mode CTFA only: engine.cpp check_active.)
+  const unsigned char* active;
 };
 // activation trace slots (floats per slot: the largest traced tensor, 256 x 128): 0 input layer [256][64]; 1 + k: output of CTFA k [F0][64]
 // (encoder stages 0..5, decoder stages 6..11); 13 + s: output of the up-sampling conv of decoder stage s [F0][128]

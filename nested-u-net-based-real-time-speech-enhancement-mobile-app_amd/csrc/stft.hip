@@ -48,9 +48,11 @@ __device__ __forceinline__ void fft512(float* re, float* im, const float2* __res
 // ph [B,257] unit phasors of bins 0..256
 __global__ __launch_bounds__(256) void stft_hop_kernel(const float* __restrict__ pcm, float* __restrict__ tail,
                                                       const float* __restrict__ win, const float2* __restrict__ tw,
-                                                      float* __restrict__ mag, float2* __restrict__ ph) {
+                                                      float* __restrict__ mag, float2* __restrict__ ph,
+                                                      const unsigned char* __restrict__ active) {
   __shared__ float re[N], im[N];
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (active && !active[b]) return;      // held stream (workgroup-uniform): its previous hop stays, nothing is written for it
   const float x_old = tail[static_cast<size_t>(b) * H + tid];
   const float x_new = pcm[static_cast<size_t>(b) * H + tid];
   tail[static_cast<size_t>(b) * H + tid] = x_new;
@@ -71,9 +73,14 @@ __global__ __launch_bounds__(256) void stft_hop_kernel(const float* __restrict__
 // pcm_out [B,256].  dc_edge: bin 0 = est[0] (PC loop) else 0 (phone).
 __global__ __launch_bounds__(256) void istft_hop_kernel(const float* __restrict__ est, const float2* __restrict__ ph,
                                                        const float* __restrict__ inv_win, const float2* __restrict__ tw,
-                                                       float* __restrict__ ola, float* __restrict__ pcm_out, int dc_edge) {
+                                                       float* __restrict__ ola, float* __restrict__ pcm_out, int dc_edge,
+                                                       const unsigned char* __restrict__ active) {
   __shared__ float re[N], im[N];
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (active && !active[b]) {            // held stream (workgroup-uniform): a zero hop, its overlap tail stays
+    pcm_out[static_cast<size_t>(b) * H + tid] = 0.f;
+    return;
+  }
   const float* e = est + static_cast<size_t>(b) * H;
   const float2* p = ph + static_cast<size_t>(b) * (H + 1);
   // Hermitian spectrum: bins 0..256 given, 257..511 mirrored; irfft ignores the imaginary parts of bins 0 and 256
@@ -94,16 +101,17 @@ __global__ __launch_bounds__(256) void istft_hop_kernel(const float* __restrict_
   ola[o] = y1;
 }
 
-hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s) {
+hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s,
+                           const unsigned char* active) {
   hipLaunchKernelGGL(stft_hop_kernel, dim3(B), dim3(256), 0, s, pcm, tail, win, reinterpret_cast<const float2*>(tw), mag,
-                     reinterpret_cast<float2*>(ph));
+                     reinterpret_cast<float2*>(ph), active);
   return hipGetLastError();
 }
 
 hipError_t launch_istft_hop(const float* est, const float* ph, const float* inv_win, const float* tw, float* ola, float* pcm_out,
-                            int dc_edge, int B, hipStream_t s) {
+                            int dc_edge, int B, hipStream_t s, const unsigned char* active) {
   hipLaunchKernelGGL(istft_hop_kernel, dim3(B), dim3(256), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
-                     reinterpret_cast<const float2*>(tw), ola, pcm_out, dc_edge);
+                     reinterpret_cast<const float2*>(tw), ola, pcm_out, dc_edge, active);
   return hipGetLastError();
 }
 

@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "nutls_offline_set_pipeline", "nutls_streams_per_workgroup", "nutls_fused_plan_blob_floats", "nutls_fused_pack_blob_plan",
     "nutls_set_ctfa_mode", "nutls_fused_plan_num_ops", "nutls_fused_plan_op_info", "nutls_create_plan",
     "nutls_enhance_block", "nutls_enhance_block_host", "nutls_stft_block", "nutls_istft_block",
+    "nutls_step_active", "nutls_step_host_active", "nutls_enhance_hop_active", "nutls_enhance_hop_host_active",
 )
 
 
@@ -107,6 +108,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_enhance_block_host.argtypes = [c.c_void_p, fp, fp, c.c_int, c.c_int]
         lib.nutls_stft_block.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]
         lib.nutls_istft_block.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_step_active"):
+        lib.nutls_step_active.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.nutls_step_host_active.argtypes = [c.c_void_p, fp, fp, c.c_void_p]
+        lib.nutls_enhance_hop_active.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]
+        lib.nutls_enhance_hop_host_active.argtypes = [c.c_void_p, fp, fp, c.c_void_p, c.c_int]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -251,11 +257,35 @@ class NutlsEngine:
         return self._lib.nutls_launches_per_step(self._h)
 
     # -- the hot path ----------------------------------------------------------------------
-    def step(self, mag, out=None):
+    def _host_mask(self, active) -> np.ndarray:
+        """``active`` of a numpy call: a length-B bool / uint8 array -> contiguous uint8 (checked before the library is called)."""
+        if not (isinstance(active, np.ndarray) and active.dtype in (np.bool_, np.uint8)):
+            raise ValueError("active must be a bool / uint8 numpy array of length %d when the frames are a numpy array" % self.batch)
+        if active.shape != (self.batch,):
+            raise ValueError("active must have length %d (one flag per stream), got shape %s" % (self.batch, active.shape))
+        return np.ascontiguousarray(active).view(np.uint8)
+
+    def _device_mask(self, active, like):
+        """``active`` of a tensor call: a length-B bool / uint8 CUDA tensor on the frames' device (read by the kernels: it must stay
+        unmodified until the queued work has run)."""
+        import torch
+        if not (torch.is_tensor(active) and active.is_cuda and active.dtype in (torch.bool, torch.uint8) and active.is_contiguous()):
+            raise ValueError("active must be a contiguous bool / uint8 CUDA tensor of length %d when the frames are a CUDA tensor" % self.batch)
+        if tuple(active.shape) != (self.batch,):
+            raise ValueError("active must have length %d (one flag per stream), got shape %s" % (self.batch, tuple(active.shape)))
+        if active.device != like.device:
+            raise ValueError("active lives on %s, the frames on %s" % (active.device, like.device))
+        return active.data_ptr()
+
+    def step(self, mag, out=None, active=None):
         """One frame for all B streams.  ``mag``: ``[B,256]`` float32, either a torch tensor on
         this engine's GPU (zero-copy, asynchronous on the current torch stream; ``out`` may be
         a preallocated tensor) or a numpy array (H2D + step + D2H, synchronous; ``out`` may be a preallocated
-        array -- with arrays from ``host_alloc`` for both there are no copies, the kernel works on them over the link)."""
+        array -- with arrays from ``host_alloc`` for both there are no copies, the kernel works on them over the link).
+        ``active`` (length-B bool / uint8: a numpy array with numpy frames, a CUDA tensor with tensor frames): only the streams whose
+        flag is nonzero take the frame, the others are HELD -- their state stays exactly as it was, their rows of ``mag`` are not used
+        and their output rows are zero (``nutls_step_active``: fused mode, LSTM variant, frame-mode CTFA; anything else raises
+        ``ValueError``).  A stream's results depend on the frames it took, not on the ticks it took them at."""
         if isinstance(mag, np.ndarray):
             m = np.ascontiguousarray(mag, dtype=np.float32)
             if m.shape != (self.batch, T.N_BINS):
@@ -266,6 +296,10 @@ class NutlsEngine:
                 o = out
                 if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.shape == m.shape):
                     raise ValueError("out must be a contiguous float32 numpy array of mag's shape")
+            if active is not None:
+                a = self._host_mask(active)
+                _check(self._lib, self._lib.nutls_step_host_active(self._h, _fptr(m), _fptr(o), a.ctypes.data))
+                return o
             _check(self._lib, self._lib.nutls_step_host(self._h, _fptr(m), _fptr(o)))
             return o
         import torch
@@ -278,17 +312,21 @@ class NutlsEngine:
         if mag.device.index != self.device or out.device != mag.device:
             raise ValueError("mag / out live on %s / %s, this engine on cuda:%d" % (mag.device, out.device, self.device))
         stream = torch.cuda.current_stream(mag.device).cuda_stream
+        if active is not None:
+            _check(self._lib, self._lib.nutls_step_active(self._h, mag.data_ptr(), out.data_ptr(), self._device_mask(active, mag), stream))
+            return out
         _check(self._lib, self._lib.nutls_step(self._h, mag.data_ptr(), out.data_ptr(), stream))
         return out
 
     # -- STFT front end / inverse-STFT back end on the device ----------------
     _DC = {"edge": 0, "zero": 1}
 
-    def enhance_hop(self, pcm, dc_mode: str = "edge", out=None):
+    def enhance_hop(self, pcm, dc_mode: str = "edge", out=None, active=None):
         """One hop (256 samples) of every stream: analysis -> model step -> synthesis, all on the
         GPU (``interpreter_proposed.py:203-213, 352-365``).  ``pcm``: ``[B,256]`` float32 numpy array
         (synchronous) or CUDA tensor (asynchronous on the current torch stream).  The output lags the
-        input by one hop, exactly like the reference loop."""
+        input by one hop, exactly like the reference loop.  ``active``: as in ``step`` -- a held stream's previous hop, overlap tail
+        and model state stay as they are, its hop of the output is zero (``nutls_enhance_hop_active``)."""
         if dc_mode not in self._DC:
             raise ValueError("dc_mode must be 'edge' or 'zero'")
         if isinstance(pcm, np.ndarray):
@@ -296,6 +334,10 @@ class NutlsEngine:
             if x.shape != (self.batch, 256):
                 raise ValueError("pcm must be [%d,256], got %s" % (self.batch, x.shape))
             o = np.empty_like(x)
+            if active is not None:
+                a = self._host_mask(active)
+                _check(self._lib, self._lib.nutls_enhance_hop_host_active(self._h, _fptr(x), _fptr(o), a.ctypes.data, self._DC[dc_mode]))
+                return o
             _check(self._lib, self._lib.nutls_enhance_hop_host(self._h, _fptr(x), _fptr(o), self._DC[dc_mode]))
             return o
         import torch
@@ -306,6 +348,10 @@ class NutlsEngine:
         if out is None:
             out = torch.empty_like(pcm)
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        if active is not None:
+            _check(self._lib, self._lib.nutls_enhance_hop_active(self._h, pcm.data_ptr(), out.data_ptr(), self._device_mask(active, pcm),
+                                                                 self._DC[dc_mode], stream))
+            return out
         _check(self._lib, self._lib.nutls_enhance_hop(self._h, pcm.data_ptr(), out.data_ptr(), self._DC[dc_mode], stream))
         return out
 
