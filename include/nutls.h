@@ -151,6 +151,31 @@ int nutls_enhance_hop_host_active(nutls_handle* h, const float* pcm_in, float* p
  * (+ phase kept inside), synthesis of one hop from the library's mag_out buffer.  Device pointers. */
 int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream);
 int nutls_istft_hop(nutls_handle* h, float* pcm_out, int dc_mode, void* stream);
+
+/* ---- Hop fusion: the streaming hop as ONE launch --------------------------------------------------------------
+ * By default nutls_enhance_hop is three launches -- analysis, model step, synthesis -- and the 256 magnitudes and 257 phasors of every
+ * stream go through device memory between them.  With hop fusion on, the four nutls_enhance_hop* entries issue one launch of a hop build of
+ * the fused step kernel: one wavefront per stream transforms the new hop in front of the first layer (a 256-point complex transform on the
+ * real frame, in registers and the wave's own shared memory), one transforms the estimate back and overlap-adds behind the last layer.
+ *   - Same state, same buffers: previous hop, overlap tail, phasors and the library's mag_in / mag_out rows (nutls_io_buffers) keep their
+ *     layouts and meanings, so fusion may be switched between any two hops of a live stream, nutls_reset works as before, and
+ *     nutls_debug_get("phasor") / the io buffers show the same things.  The transform is the waveform block mode's (nutls_stft_block), not
+ *     the three-launch path's radix-2 one: outputs agree with the three-launch path to rounding (1e-5 relative RMS), not bit for bit.
+ *   - Masks: nutls_enhance_hop_active behaves as documented above -- held rows of pcm_out are zero hops, a held stream's previous hop,
+ *     overlap tail and phasors stay, its pcm_in row is not read where its whole workgroup is held.
+ *   - Host buffers: when BOTH buffers of nutls_enhance_hop_host(_active) come from nutls_host_alloc the kernel reads and writes them over
+ *     the link itself (no copy commands); pageable buffers keep the staged copies.
+ *   - Unchanged: nutls_stft_hop, nutls_istft_hop, nutls_step* and every call on a handle with fusion off run the kernels they always ran.
+ * Default: off.  NUTLS_HOP_FUSION=1 in the environment at creation turns it on for handles that support it (quietly off elsewhere).
+ *
+ * Supported: streaming handles of the LSTM variant in the fused mode (mode 3) on the one- and two-stream plans, either CTFA mode.
+ * nutls_set_hop_fusion(h, nonzero) returns NUTLS_ERR_ARG (reason in nutls_last_error) and changes nothing on: the baseline variant, the
+ * four-stream plan, modes 0 / 1, offline handles, a handle with nutls_debug_trace on.  While fusion is on, nutls_debug_trace(h, 1),
+ * nutls_set_mode(h, 0 or 1), nutls_use_graph and the nutls_profile_* entries are refused the same way: an explicit request for one
+ * launch per hop never silently becomes three.  nutls_set_hop_fusion(h, 0) always succeeds.
+ * nutls_launches_per_hop: 3, or 1 with fusion on. */
+int nutls_set_hop_fusion(nutls_handle* h, int enable);
+int nutls_launches_per_hop(nutls_handle* h);
 /* Waveform block mode: the same front end / back end for OFFLINE handles (nutls_create_offline, nutls_create_offline_batch; a streaming
  * handle gets NUTLS_ERR_ARG), a whole block per call -- the loop of interpreter_proposed.py:203-213, 352-365 over n_hops hops of every
  * utterance in one analysis launch and one synthesis launch around nutls_process_block.

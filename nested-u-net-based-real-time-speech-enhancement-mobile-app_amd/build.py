@@ -19,9 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libnutls_hip.so")
-SOURCES = ["fused_step.hip", "fused_step_g2.hip", "fused_step_g4.hip", "fused_step_prof.hip", "fused_step_stop.hip", "fused_base.hip", "fused_base_prof.hip", "kernels.hip", "stft.hip", "stft_block.hip", "offline.hip", "weights.cpp", "fused_host.cpp", "engine.cpp"]
+SOURCES = ["fused_step.hip", "fused_step_g2.hip", "fused_step_g4.hip", "fused_step_hop.hip", "fused_step_g2_hop.hip", "fused_step_prof.hip", "fused_step_stop.hip", "fused_base.hip", "fused_base_prof.hip", "kernels.hip", "stft.hip", "stft_block.hip", "offline.hip", "weights.cpp", "fused_host.cpp", "engine.cpp"]
 if os.environ.get("NUTLS_BUILD_G4_PROF") == "1":      # developer knob: the profiling twin of the 4-stream packed kernel (12 more minutes)
     SOURCES.insert(3, "fused_step_g4_prof.hip")
+# (fused_step_hop.hip / fused_step_g2_hop.hip: the hop builds of the one- and two-stream kernels, nutls_set_hop_fusion)
 # (headers are found by scanning the #include "..." lines of every source: _deps)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # The 4-stream packed kernel is one very large function, and LLVM's SDWA peephole (which only re-encodes sub-dword operand
@@ -111,7 +112,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     import time
     t0 = time.time()
     # (the longest compiles first: the 4-stream packed kernel alone is about 12 minutes, the pool must not start it last)
-    order = sorted(todo, key=lambda s: {"fused_step_g4.hip": 0, "fused_step_g4_prof.hip": 0, "fused_step_g2.hip": 1}.get(s, 2))
+    order = sorted(todo, key=lambda s: {"fused_step_g4.hip": 0, "fused_step_g4_prof.hip": 0, "fused_step_g2.hip": 1, "fused_step_g2_hop.hip": 1}.get(s, 2))
     with ThreadPoolExecutor(max_workers=6) as ex:
         list(ex.map(lambda s: _compile(hipcc, s, verbose), order))
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + [_obj(s) for s in SOURCES], verbose)

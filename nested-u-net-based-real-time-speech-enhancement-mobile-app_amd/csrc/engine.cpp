@@ -139,6 +139,8 @@ struct Engine {
   // STFT front / back end (allocated on first use): previous hop, overlap tail, phasors, windows, twiddles, staging
   float *fe_tail = nullptr, *fe_ola = nullptr, *fe_ph = nullptr, *fe_win = nullptr, *fe_inv = nullptr, *fe_tw = nullptr;
   float *fe_pcm_in = nullptr, *fe_pcm_out = nullptr;
+  float* fe_twb = nullptr;       // stft_block_twiddles(): the wave-level transform of the hop builds of the fused kernel
+  bool hop_fusion = false;       // nutls_set_hop_fusion: the nutls_enhance_hop* entries run ONE launch (FusedPlan::launch_hop) instead of three
   // waveform block mode of an offline handle (stft_block.hip; allocated on first use): previous hop and overlap tail of every utterance [outt][256],
   // two buffers each -- a launch reads [par] and writes [1 - par] --, the phasors of the last analysed block [outt][fb_hops][257] float2, windows,
   // twiddles (stft_block_twiddles) and, for the host entry, PCM staging [outt][offline * 256]
@@ -992,12 +994,16 @@ static int ysum_refresh(Engine* e, int par, hipStream_t s) {
 
 // (mag_in / mag_out: the caller's device buffers, read by the input layer and written by the last op directly -- no staging copies)
 // (active: device mask of nutls_step_active, null = every stream takes the frame)
+// (hop: the single-launch hop of nutls_set_hop_fusion -- the plan's hop build analyses hop->pcm_in in front of the step and synthesises
+//  hop->pcm_out behind it; the caller fills in the two PCM pointers and dc_edge, the handle's front / back end buffers are added here)
 static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* mag_in = nullptr, float* mag_out = nullptr,
-                     const unsigned char* active = nullptr) {
+                     const unsigned char* active = nullptr, const FzHop* hop = nullptr) {
   if (!e->fz_blob) return fail(NUTLS_ERR_ARG, "fused mode is not available for this handle");
   const bool base = e->variant == NUTLS_VARIANT_BASELINE;
+  if (hop && (!e->fz_plan->launch_hop || !e->fe_twb || prof || e->fz_stop_at >= 0))
+    return fail(NUTLS_ERR_ARG, "single-launch hop: not available for this handle (nutls_set_hop_fusion)");
   if (int rc = ysum_refresh(e, par, s)) return rc;
-  auto launch = e->fz_plan->launch;
+  auto launch = hop ? e->fz_plan->launch_hop : e->fz_plan->launch;
   int skew = e->fz_skew;            // (NUTLS_FUSED_SKEW at creation, nutls_debug_knob(h, "skew", v) later)
   if (e->fz_stop_at >= 0) {         // (nutls_profile_production: one-stream LSTM plan only, checked there)
     launch = launch_fused_step_stop;
@@ -1020,6 +1026,7 @@ static int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* 
     ta = FzTa{e->fz_ta_sum, e->fz_ta_ring + slot * 64, 12 * 64, 64, 12 * 32 * 64, 32 * 64, skew, eager, dbg, dbg_ss};
   }
   ta.active = active;
+  if (hop) ta.hop = FzHop{hop->pcm_in, hop->pcm_out, e->fe_tail, e->fe_ola, e->fe_ph, e->fe_win, e->fe_inv, e->fe_twb, hop->dc_edge};
   hipError_t err = launch(e->arena, static_cast<long long>(e->sstride), e->fz_blob, mag_in ? mag_in : e->io_in,
                           mag_out ? mag_out : e->io_out, e->B, par, prof ? e->fz_prof : nullptr,
                           base ? e->d_ddb : nullptr, static_cast<int>(e->steps & 0x3fffffff), e->B / e->fz_plan->streams, s, ta);
@@ -1111,6 +1118,9 @@ static int frontend_init(Engine* e) {
     return rc;
   std::vector<float> win, inv, tw;
   frontend_tables(&win, &inv, &tw);
+  const std::vector<float> twb = stft_block_twiddles();      // (the hop builds of the fused kernel: nutls_set_hop_fusion)
+  if ((rc = dalloc(&e->fe_twb, twb.size()))) return rc;
+  HIP_TRY(hipMemcpy(e->fe_twb, twb.data(), twb.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->fe_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->fe_inv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->fe_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1259,6 +1269,15 @@ static int create_body(const void* weights, size_t n_bytes, int variant, int bat
     if (rc) return rc;
     if (e->fz_blob) {
       e->mode = 3;          // the default for streaming handles whose container holds int8 conv kernels
+      // NUTLS_HOP_FUSION=1: the nutls_enhance_hop* entries of this handle run one launch per hop where a hop build exists (LSTM variant, one-
+      // and two-stream plans) -- the switch nutls_set_hop_fusion turns, for callers that cannot be edited (bench.py --frontend); quietly off elsewhere
+      if (const char* ev = getenv("NUTLS_HOP_FUSION")) {
+        if (atoi(ev) != 0 && variant == NUTLS_VARIANT_LSTM && e->fz_plan->launch_hop) {
+          if ((rc = frontend_init(e))) return rc;
+          HIP_TRY(e->fz_plan->set_attributes_hop());
+          e->hop_fusion = true;
+        }
+      }
     } else {
       // float containers: the per-layer kernels, replayed as a hipGraph -- the same default for C and Python callers
       if ((rc = capture_graphs(e))) return rc;
@@ -1589,9 +1608,18 @@ static int refuse_per_layer_in_causal32(const Engine* e, const char* who) {
   return NUTLS_OK;
 }
 
+// While hop fusion is on (nutls_set_hop_fusion) the handle stays what the single launch needs -- fused mode, production kernel: whatever would
+// take it elsewhere refuses, so that an explicit request for one launch per hop never silently becomes three.
+static int refuse_in_hop_fusion(const Engine* e, const char* who) {
+  if (e->hop_fusion)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": not while hop fusion is on (the single-launch hop runs the fused production kernel) -- nutls_set_hop_fusion(h, 0) first");
+  return NUTLS_OK;
+}
+
 int nutls_use_graph(nutls_handle* h, int enable) {
   if (!h) return fail(NUTLS_ERR_ARG, "null handle");
   Engine* e = &h->eng;
+  if (int rc = refuse_in_hop_fusion(e, "nutls_use_graph")) return rc;
   if (int rc = refuse_per_layer_in_causal32(e, "nutls_use_graph")) return rc;
   HIP_TRY(hipSetDevice(e->device));
   if (enable) {
@@ -1609,6 +1637,8 @@ int nutls_set_mode(nutls_handle* h, int mode) {
     return fail(NUTLS_ERR_ARG, "nutls_set_mode: mode 3 (fused kernel) needs a streaming handle made from a container with int8 conv kernels" +
                                    (h->eng.fz_reason.empty() ? std::string() : " (" + h->eng.fz_reason + ")"));
   if (h->eng.offline && mode != 0) return fail(NUTLS_ERR_ARG, "nutls_set_mode: offline handles run per-layer launches (mode 0)");
+  if (mode != 3)
+    if (int rc = refuse_in_hop_fusion(&h->eng, "nutls_set_mode")) return rc;
   if (mode != 3)
     if (int rc = refuse_per_layer_in_causal32(&h->eng, "nutls_set_mode")) return rc;
   if (mode == 1) return nutls_use_graph(h, 1);
@@ -1811,8 +1841,53 @@ static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const un
   return NUTLS_OK;
 }
 
+// ---- single-launch hop (nutls_set_hop_fusion) -------------------------------------------------------------------------------------------
+// Where the hop builds of the fused kernel exist: streaming handles of the LSTM variant in the fused mode on the one- or two-stream plan,
+// production kernel (no activation trace, no stop twin).  Everything else refuses -- never a silent three-launch hop.
+static int check_hop_fusion(const Engine* e, const char* who) {
+  const std::string w = std::string(who) + ": the single-launch hop ";
+  if (e->offline) return fail(NUTLS_ERR_ARG, w + "needs a streaming handle (an offline handle takes PCM through nutls_enhance_block)");
+  if (e->variant != NUTLS_VARIANT_LSTM) return fail(NUTLS_ERR_ARG, w + "is not built for the baseline variant (hop builds: LSTM variant, one- and two-stream plans)");
+  if (e->mode != 3 || !e->fz_blob) return fail(NUTLS_ERR_ARG, w + "is a build of the fused kernel (mode 3): modes 0 / 1 run one kernel per layer -- nutls_set_mode(h, 3) first");
+  if (!e->fz_plan->launch_hop)
+    return fail(NUTLS_ERR_ARG, w + "is not built for the " + std::to_string(e->fz_plan->streams) + "-stream plan (nutls_create_plan(..., 1) or (..., 2))");
+  if (e->fz_dbg) return fail(NUTLS_ERR_ARG, w + "runs the production kernel, the activation trace the profiling build -- nutls_debug_trace(h, 0) first");
+  if (e->fz_stop_at >= 0) return fail(NUTLS_ERR_ARG, w + "cannot be combined with nutls_profile_production");
+  return NUTLS_OK;
+}
+
+int nutls_set_hop_fusion(nutls_handle* h, int enable) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_hop_fusion: null handle");
+  Engine* e = &h->eng;
+  if (!enable) { e->hop_fusion = false; return NUTLS_OK; }
+  if (int rc = check_hop_fusion(e, "nutls_set_hop_fusion")) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = frontend_init(e)) return rc;
+  HIP_TRY(e->fz_plan->set_attributes_hop());
+  e->hop_fusion = true;
+  return NUTLS_OK;
+}
+
+int nutls_launches_per_hop(nutls_handle* h) { return h ? (h->eng.hop_fusion ? 1 : 3) : fail(NUTLS_ERR_ARG, "null handle"); }
+
+// analysis, model step and synthesis in ONE launch of the plan's hop build: magnitudes and estimates still go through the library's io rows, the
+// previous hops / overlap tails / phasors through the buffers of the three-launch path -- fusion may change between any two hops of a stream
+static int enhance_hop_fused(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  if (dc_mode != NUTLS_DC_EDGE && dc_mode != NUTLS_DC_ZERO) return fail(NUTLS_ERR_ARG, "dc_mode must be NUTLS_DC_EDGE or NUTLS_DC_ZERO");
+  Engine* e = &h->eng;
+  if (int rc = check_hop_fusion(e, "nutls_enhance_hop")) return rc;      // (cannot fail: everything that would is refused while fusion is on)
+  HIP_TRY(hipSetDevice(e->device));
+  const FzHop hop{pcm_in, pcm_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dc_mode == NUTLS_DC_EDGE ? 1 : 0};
+  const int par = e->next_parity;
+  if (int rc = run_fused(e, par, static_cast<hipStream_t>(stream), false, e->io_in, e->io_out, active, &hop)) return rc;
+  e->next_parity = 1 - par;
+  e->steps += 1;
+  return NUTLS_OK;
+}
+
 // analysis -> model step on the library buffers -> synthesis, all three with the (device) mask or without one
 static int enhance_hop_impl(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  if (h->eng.hop_fusion) return enhance_hop_fused(h, pcm_in, pcm_out, active, dc_mode, stream);
   int rc = stft_hop_impl(h, pcm_in, active, stream);
   if (rc) return rc;
   Engine* e = &h->eng;
@@ -1864,6 +1939,14 @@ static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pc
   if (active) {
     if ((rc = upload_active(e, active))) return rc;
     d_act = e->d_active;
+  }
+  if (e->hop_fusion && host_pinned(pcm_in, bytes) && host_pinned(pcm_out, bytes)) {
+    // the hop build takes the caller's page-locked buffers as they are (like step_host_impl): two 1 KB rows per stream cross the link inside
+    // the launch, no copy commands
+    if ((rc = enhance_hop_impl(h, pcm_in, pcm_out, d_act, dc_mode, e->stream))) return rc;
+    if (active) note_active(e, active);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return NUTLS_OK;
   }
   HIP_TRY(hipMemcpyAsync(e->fe_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
   if ((rc = enhance_hop_impl(h, e->fe_pcm_in, e->fe_pcm_out, d_act, dc_mode, e->stream))) return rc;
@@ -2162,6 +2245,7 @@ int nutls_debug_trace(nutls_handle* h, int enable) {
   if (!h) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: null handle");
   Engine* e = &h->eng;
   if (!enable) { e->fz_dbg = nullptr; return NUTLS_OK; }      // (the buffer stays allocated with the handle)
+  if (int rc = refuse_in_hop_fusion(e, "nutls_debug_trace")) return rc;      // (the trace is the profiling build's; the hop builds have none)
   if (e->offline || !e->fz_blob) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: the activation trace is the fused kernel's (streaming handle, int8 container)");
   if (e->fz_plan->streams != 1) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: the packed plans have no profiling build in the library (nutls_create_plan(..., 1) for the one-stream plan)");
   if (e->B > 64) return fail(NUTLS_ERR_ARG, "nutls_debug_trace: at most 64 streams (2.5 MB of trace per stream)");
@@ -2246,6 +2330,7 @@ int nutls_profile_step(nutls_handle* h, float* ms, int n) {
   const int par = e->next_parity;
   const std::vector<Launch>& plan = e->plan[par];
   if (n != static_cast<int>(plan.size())) return fail(NUTLS_ERR_ARG, "nutls_profile_step: n must equal nutls_launches_per_step");
+  if (int rc = refuse_in_hop_fusion(e, "nutls_profile_step")) return rc;
   if (int rc = refuse_per_layer_in_causal32(e, "nutls_profile_step")) return rc;
   HIP_TRY(hipSetDevice(e->device));
   std::vector<hipEvent_t> ev(plan.size() + 1);
@@ -2329,6 +2414,7 @@ int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, i
   if (e->offline || e->mode != 3 || !e->fz_blob || e->variant != NUTLS_VARIANT_LSTM || e->fz_plan->streams != 1 || e->ctfa_causal)
     return fail(NUTLS_ERR_ARG, "nutls_profile_production: a streaming handle of the LSTM variant in the fused mode on the one-stream plan, per-frame CTFA "
                                "(the stop twin exists for that kernel only)");
+  if (int rc = refuse_in_hop_fusion(e, "nutls_profile_production")) return rc;
   const int nops = e->fz_plan->num_ops;
   if (n != nops + 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: n must equal nutls_fused_num_ops(variant) + 1");
   if (reps < 1 || steps < 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: reps and steps must be positive");
@@ -2372,6 +2458,7 @@ int nutls_profile_fused(nutls_handle* h, double* us, int n) {
   Engine* e = &h->eng;
   if (n != e->fz_plan->num_ops)
     return fail(NUTLS_ERR_ARG, "nutls_profile_fused: n must equal nutls_fused_plan_num_ops(variant, nutls_streams_per_workgroup(h))");
+  if (int rc = refuse_in_hop_fusion(e, "nutls_profile_fused")) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const int par = e->next_parity;
   int rc = run_fused(e, par, e->stream, true);

@@ -82,8 +82,9 @@ std::vector<int> channel_perm(const fz::OpD& d) {
 
 // The only place that knows which plans exist, and which kernel runs which.
 const FusedPlan* fused_plan(int variant, int streams) {
-  if (variant == NUTLS_VARIANT_LSTM && streams == 1) return lstm_plan::describe(variant, launch_fused_step, fused_step_set_attributes);
-  if (variant == NUTLS_VARIANT_LSTM && streams == 2) return lstm_g2_plan::describe(variant, launch_fused_step_g2, fused_step_g2_set_attributes);
+  if (variant == NUTLS_VARIANT_LSTM && streams == 1) return lstm_plan::describe(variant, launch_fused_step, fused_step_set_attributes, launch_fused_step_hop, fused_step_hop_set_attributes);
+  if (variant == NUTLS_VARIANT_LSTM && streams == 2) return lstm_g2_plan::describe(variant, launch_fused_step_g2, fused_step_g2_set_attributes, launch_fused_step_g2_hop,
+                                  fused_step_g2_hop_set_attributes);
   if (variant == NUTLS_VARIANT_LSTM && streams == 4) return lstm_g4_plan::describe(variant, launch_fused_step_g4, fused_step_g4_set_attributes);
   if (variant == NUTLS_VARIANT_BASELINE && streams == 1) return base_plan::describe(variant, launch_fused_base_step, fused_base_step_set_attributes);
   return nullptr;

@@ -28,6 +28,9 @@ struct FusedPlan {
   // the plan's kernel (each dispatches to its profiling twin itself when `prof` is non-null)
   decltype(&launch_fused_step) launch;
   hipError_t (*set_attributes)();
+  // the plan's hop build (FZ_HOP: STFT analysis and inverse STFT inside the launch, nutls_set_hop_fusion), null where none is built
+  decltype(&launch_fused_step) launch_hop;
+  hipError_t (*set_attributes_hop)();
 };
 
 // The plans that exist: 1 / 2 / 4 streams per workgroup for the LSTM variant, 1 for the baseline.  nullptr: no such plan.

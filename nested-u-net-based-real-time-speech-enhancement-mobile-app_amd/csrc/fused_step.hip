@@ -65,6 +65,18 @@
 #if FZ_BASE && FZ_STREAMS != 1
 #error "packed plans exist for the LSTM variant only"
 #endif
+// FZ_HOP = 1: the hop builds (fused_step_hop.hip / fused_step_g2_hop.hip, nutls_set_hop_fusion): the streaming loop's STFT analysis runs in front of
+// op 0 and its inverse STFT / overlap-add behind the last op (hop_prologue / hop_epilogue below, FzHop) -- PCM hop in, PCM hop out, one launch.
+// No op changes: the other builds compile what they compiled without it.
+#ifndef FZ_HOP
+#define FZ_HOP 0
+#endif
+#if FZ_HOP && (FZ_BASE || FZ_PROF || FZ_STOPAT || FZ_STREAMS > 2)
+#error "hop builds exist for the one- and two-stream production kernels of the LSTM variant"
+#endif
+#if FZ_HOP
+#include "stft_wave.hpp"
+#endif
 
 namespace nutls {
 namespace fz {
@@ -1652,7 +1664,101 @@ __device__ __forceinline__ int ticket_tid() {
   return static_cast<int>(w * 64u + lane);
 }
 
-#if FZ_STREAMS == 2
+#if FZ_HOP
+// ---- single-launch hop (FZ_HOP builds; FzHop, nutls_set_hop_fusion) -----------------------------------------------------------------------
+// Wave g < NSTREAMS owns stream slot g of the workgroup for the front and back end: one wavefront transforms one 512-sample frame with the
+// barrier-free wave-level transform of the waveform block mode (stft_wave.hpp), on an LDS image of its own at the start of `lds` (free in
+// front of op 0 and behind the last op; the first 16 bytes stay with ticket_tid's counter).  Same buffers, layouts and results as
+// stft_hop_kernel / istft_hop_kernel of stft.hip, which the three-launch path runs: a handle may switch between the two from hop to hop.
+constexpr int kHopImage0 = 2;      // float2 slots in front of the first image (ticket_tid's counter lives in the first dword)
+static_assert((kHopImage0 + NSTREAMS * stftw::kWaveImage) * 8 <= LDS_BYTES && NSTREAMS <= THREADS / 64, "LDS images of the hop front / back end");
+
+// In front of op 0.  `act`: active_bits (all ones without a mask); a held slot's wave leaves its previous hop, magnitudes and phasors alone.
+// Ends with every wave of the workgroup seeing the rows of io_in: op 0 reads them as it does in every other build.
+__device__ __forceinline__ void hop_prologue(const FzArgs& a, int stream, unsigned act) {
+  const FzHop& hp = a.ta.hop;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  if (wave < NSTREAMS && ((act >> wave) & 1u)) {
+    const size_t b = static_cast<size_t>(stream + wave);
+    float2* buf = reinterpret_cast<float2*>(lds) + kHopImage0 + wave * stftw::kWaveImage;
+    const float2* tw = reinterpret_cast<const float2*>(hp.tw);
+    const stftw::Twiddles t = stftw::load_twiddles(tw, lane);
+    float2 w[4], ws[4];
+    stftw::load_analysis_regs(hp.win, tw, lane, w, ws);
+    float2* tail = reinterpret_cast<float2*>(hp.tail + b * 256);
+    const float2* cur = reinterpret_cast<const float2*>(hp.pcm_in + b * 256);
+    const float2 p0 = tail[lane], p1 = tail[lane + 64];
+    const float2 c0 = cur[lane], c1 = cur[lane + 64];
+    tail[lane] = c0; tail[lane + 64] = c1;                                     // the new hop is the next frame's previous hop
+    float m[4];
+    float2 rot[4], dc;
+    stftw::analyse_frame(p0, p1, c0, c1, w, ws, t, buf, lane, m, rot, dc);
+    float2* mrow = reinterpret_cast<float2*>(const_cast<float*>(a.io_in) + b * 256);
+    mrow[lane] = make_float2(m[0], m[1]);
+    mrow[lane + 64] = make_float2(m[2], m[3]);
+    float2* prow = reinterpret_cast<float2*>(hp.ph) + b * 257;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) prow[2 * lane + 1 + (i & 1) + 128 * (i >> 1)] = rot[i];
+    if (lane == 0) prow[0] = dc;
+  }
+  // the rows are in memory and the images free before any wave goes on: release, wait for the stores, workgroup barrier, acquire
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// a wholly held workgroup: a zero hop for each of its streams, nothing else of the front / back end moves
+__device__ __forceinline__ void hop_hold_all(const FzArgs& a, int stream) {
+  const int tid = threadIdx.x;
+  if (tid < 128 * NSTREAMS) reinterpret_cast<float2*>(a.ta.hop.pcm_out + static_cast<size_t>(stream) * 256)[tid] = make_float2(0.f, 0.f);
+}
+
+// Behind the last op.  Like the hold path behind the step it owes nothing to the step's registers: the arguments are re-read from the
+// kernel-argument segment and the wave index is a ticket (any wave may take any slot; the prologue's images are long gone).
+__device__ __forceinline__ void hop_epilogue() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const FzArgs* ka = (const FzArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  const int t = ticket_tid();
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+  if (wave >= NSTREAMS) return;
+  const int strm = __builtin_amdgcn_workgroup_id_x() * NSTREAMS;
+  const size_t b = static_cast<size_t>(strm + wave);
+  const FzHop& hp = ka->ta.hop;
+  float2* orow = reinterpret_cast<float2*>(hp.pcm_out + b * 256);
+  if (ka->ta.active && !((active_bits(ka->ta.active, strm) >> wave) & 1u)) {      // held slot of a mixed group: a zero hop, its overlap tail stays
+    orow[lane] = make_float2(0.f, 0.f); orow[lane + 64] = make_float2(0.f, 0.f);
+    return;
+  }
+  float2* buf = reinterpret_cast<float2*>(lds) + kHopImage0 + wave * stftw::kWaveImage;
+  const float2* tw = reinterpret_cast<const float2*>(hp.tw);
+  const stftw::Twiddles tws = stftw::load_twiddles(tw, lane);
+  float2 iw[4], ws[4];
+  stftw::load_synthesis_regs(hp.inv_win, tw, lane, iw, ws);
+  float2* ola = reinterpret_cast<float2*>(hp.ola + b * 256);
+  const float2 carry0 = ola[lane], carry1 = ola[lane + 64];
+  float2 v[4];
+  stftw::synthesise_frame(reinterpret_cast<const float2*>(ka->io_out + b * 256), reinterpret_cast<const float2*>(hp.ph) + b * 257, hp.dc_edge, iw, ws, tws,
+                          buf, lane, v);
+  orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);
+  orow[lane + 64] = make_float2(carry1.x + v[1].x, carry1.y + v[1].y);
+  ola[lane] = v[2]; ola[lane + 64] = v[3];
+}
+#endif
+
+#if FZ_HOP && FZ_STREAMS == 2
+#define FZ_KERNEL nutls_fused_step_g2_hop_kernel
+#define FZ_LAUNCH launch_fused_step_g2_hop
+#define FZ_ATTR fused_step_g2_hop_set_attributes
+#define FZ_NO_PROF_TWIN 1
+#elif FZ_HOP
+#define FZ_KERNEL nutls_fused_step_hop_kernel
+#define FZ_LAUNCH launch_fused_step_hop
+#define FZ_ATTR fused_step_hop_set_attributes
+#define FZ_NO_PROF_TWIN 1
+#elif FZ_STREAMS == 2
 #define FZ_KERNEL nutls_fused_step_g2_kernel
 #define FZ_LAUNCH launch_fused_step_g2
 #define FZ_ATTR fused_step_g2_set_attributes
@@ -1763,9 +1869,15 @@ __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
     if (active_bits(a.ta.active, stream) == 0u) {
 #pragma unroll
       for (int g = 0; g < NSTREAMS; ++g) hold_stream(a.arena, a.sstride, a.io_out, a.par, stream + g, threadIdx.x);
+#if FZ_HOP
+      hop_hold_all(a, stream);
+#endif
       return;
     }
   }
+#if FZ_HOP
+  hop_prologue(a, stream, a.ta.active ? active_bits(a.ta.active, stream) : (1u << NSTREAMS) - 1u);
+#endif
   Carry<0> c0;
   {
     int tid = threadIdx.x;
@@ -1773,6 +1885,9 @@ __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
     prefetch_y<1>(cx, tid, c0.yp2);
   }
   run_from<0, PROF>(cx, c0);
+#if FZ_HOP
+  hop_epilogue();      // (before the hold path of a mixed group: that one starts with a workgroup barrier of its own and touches the held slots only)
+#endif
   if constexpr (NSTREAMS > 1) {
     // A packed group with held AND active slots ran the step for all of them (the packed ops need no masked variants); once every
     // store of the step has landed, the hold path overwrites what it wrote for the held slots.

@@ -236,6 +236,16 @@ std::vector<float> pack_conv_weights_bf16(const HostTensor& w, const std::vector
 // row of 64 zeros and `ring` one dump row, all strides 0 -- the branch sees TA / 32.  Causal32 mode (the offline model's `ctfa`,
 // proposed.py:125-160): `sum` [B][12][64] = the time attention summed over the 31 frames before this one (ta_sum_kernel, launched in
 // front of the step), `ring` points at this frame's row of the history [B][12][32][64] (row = frame mod 32); strides in floats.
+// Single-launch streaming hop (FZ_HOP builds): the step kernel analyses the new PCM hop in front of op 0 and synthesises the enhanced hop behind the
+// last op.  pcm_in / pcm_out [B][256] (device memory or page-locked host memory); tail / ola / ph: the handle's previous hops, overlap tails and
+// phasors ([B][256], [B][256], [B][257] float2 -- the buffers of launch_stft_hop / launch_istft_hop, same layout and meaning); win / inv_win as
+// there; tw = stft_block_twiddles() on the device.  The magnitudes go through the launch's io_in rows, the estimates through its io_out rows.
+struct FzHop {
+  const float* pcm_in; float* pcm_out;
+  float* tail; float* ola; float* ph;
+  const float* win; const float* inv_win; const float* tw;
+  int dc_edge;
+};
 struct FzTa {
   const float* sum; float* ring; int sum_sstride, sum_gstride, ring_sstride, ring_gstride;
   // (rides along: start skew of the workgroups, in units of 64 clocks -- workgroup w sleeps (w mod 4) * skew before its first op, so that
@@ -252,6 +262,9 @@ struct FzTa {
   //  byte is 0 is HELD: the kernel copies its `prev` parity block and carried sums onto the `cur` side and zeroes its output row --
   //  fused_step.hip hold_stream.  LSTM variant, frame-mode CTFA only: engine.cpp check_active.)
   const unsigned char* active;
+  // (and: the front / back end of the hop builds, FZ_HOP -- fused_step_hop.hip / fused_step_g2_hop.hip, nutls_set_hop_fusion.  Every other
+  //  build ignores it; launch_fused_step_hop / _g2_hop need all of it.)
+  FzHop hop;
 };
 // activation trace slots (floats per slot: the largest traced tensor, 256 x 128): 0 input layer [256][64]; 1 + k: output of CTFA k [F0][64]
 // (encoder stages 0..5, decoder stages 6..11); 13 + s: output of the up-sampling conv of decoder stage s [F0][128]
@@ -279,5 +292,12 @@ hipError_t fused_step_g2_set_attributes();
 hipError_t launch_fused_step_g4(float* arena, long long sstride, const float* blob, const float* io_in, float* io_out, int B, int par,
                                 unsigned long long* prof, const DdbParams* ddb, int step, int grid, hipStream_t s, const FzTa& ta);
 hipError_t fused_step_g4_set_attributes();
+// hop builds of the one- and two-stream kernels (fused_step_hop.hip / fused_step_g2_hop.hip): ta.hop must be filled in; `prof` must be null
+hipError_t launch_fused_step_hop(float* arena, long long sstride, const float* blob, const float* io_in, float* io_out, int B, int par,
+                                 unsigned long long* prof, const DdbParams* ddb, int step, int grid, hipStream_t s, const FzTa& ta);
+hipError_t fused_step_hop_set_attributes();
+hipError_t launch_fused_step_g2_hop(float* arena, long long sstride, const float* blob, const float* io_in, float* io_out, int B, int par,
+                                    unsigned long long* prof, const DdbParams* ddb, int step, int grid, hipStream_t s, const FzTa& ta);
+hipError_t fused_step_g2_hop_set_attributes();
 
 }  // namespace nutls

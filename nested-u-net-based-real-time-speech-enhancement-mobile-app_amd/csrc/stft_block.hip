@@ -37,94 +37,31 @@
 //               synthesis, lane l:          read  [nat(l + 64 a)]
 //   synthesis, spectrum in front of the FFT:  write [spec(k)], k = 2 l + e + 128 j, spec(k) = k ^ (bit 4 of k -> bit 0), bin 256 at [256]
 //                                             read  [spec(l + 64 a)], [spec(256 - l - 64 a)]
+// The wave-level code itself (fft256, nat, spec, the per-frame analysis and synthesis bodies) is stft_wave.hpp, shared with the hop builds
+// of the frame-step kernel.  Its index expressions, as written there (tools/check_stft_block_lds.py models exactly these):
+//   nat(k):      return k ^ (((k >> 4) & 1) << 1) ^ ((k >> 5) & 1);
+//   spec(k):     return k ^ ((k >> 4) & 1);
+//   exchange 1:  buf[80 * q + lane]                             ->  buf[80 * k0 + l0 + 16 * a]
+//   exchange 2:  buf[80 * k0 + 20 * q + l0]                     ->  buf[80 * k0 + 20 * k1 + l00 + 4 * a]
+//   exchange 3:  buf[80 * k0 + 20 * k1 + 4 * l00 + (q ^ l00)]   ->  buf[80 * k0 + 20 * k1 + 4 * a + (l00 ^ a)]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "nutls_internal.hpp"
+#include "stft_wave.hpp"
 
 namespace nutls {
 
 namespace {
 
+using namespace stftw;      // the wave-level transform and the per-frame bodies: stft_wave.hpp
+
 constexpr int H = NUTLS_FRAME_STEP;     // 256
 constexpr int kWaves = 4;               // wavefronts per workgroup
 constexpr int kRun = 4;                 // consecutive frames per wavefront: 16 frames per workgroup, 512 workgroups at 8 x 1024 frames
 constexpr int kImage = 320;             // float2 per wave
-
-// twiddle table (float2 entries; stft_block_twiddles): W256^(l q) [l][q - 1], W64^(l0 q) [l0][q - 1], W16^(l00 q) [l00][q - 1], W512^k k = 0..256
-constexpr int kTwA = 0, kTwB = kTwA + 64 * 3, kTwC = kTwB + 16 * 3, kTwS = kTwC + 4 * 3, kTwEntries = 512;
-static_assert(kTwS + 257 <= kTwEntries, "twiddle table");
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-__device__ __forceinline__ int nat(int k) { return k ^ (((k >> 4) & 1) << 1) ^ ((k >> 5) & 1); }
-__device__ __forceinline__ int spec(int k) { return k ^ ((k >> 4) & 1); }
-
-// y[q] = sum_a x[a] (-i)^(a q)
-__device__ __forceinline__ void bfly4(float2 (&x)[4]) {
-  const float2 s02 = make_float2(x[0].x + x[2].x, x[0].y + x[2].y), d02 = make_float2(x[0].x - x[2].x, x[0].y - x[2].y);
-  const float2 s13 = make_float2(x[1].x + x[3].x, x[1].y + x[3].y), d13 = make_float2(x[1].x - x[3].x, x[1].y - x[3].y);
-  x[0] = make_float2(s02.x + s13.x, s02.y + s13.y);
-  x[1] = make_float2(d02.x + d13.y, d02.y - d13.x);
-  x[2] = make_float2(s02.x - s13.x, s02.y - s13.y);
-  x[3] = make_float2(d02.x - d13.y, d02.y + d13.x);
-}
-
-struct Twiddles { float2 a[3], b[3], c[3]; };
-
-__device__ __forceinline__ Twiddles load_twiddles(const float2* __restrict__ tw, int lane) {
-  Twiddles t;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    t.a[q] = tw[kTwA + lane * 3 + q];
-    t.b[q] = tw[kTwB + (lane & 15) * 3 + q];
-    t.c[q] = tw[kTwC + (lane & 3) * 3 + q];
-  }
-  return t;
-}
-
-// Forward 256-point complex FFT of one wave.  In: lane l holds x[a] = z[l + 64 a].  Out: Z[k] at buf[nat(k)], visible to the whole wave.
-__device__ __forceinline__ void fft256(float2 (&x)[4], float2* buf, const Twiddles& t, int lane) {
-  const int k0 = lane >> 4, l0 = lane & 15, k1 = (lane >> 2) & 3, l00 = lane & 3;
-  bfly4(x);
-#pragma unroll
-  for (int q = 1; q < 4; ++q) x[q] = cmul(x[q], t.a[q - 1]);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) buf[80 * q + lane] = x[q];
-  wave_sync();
-#pragma unroll
-  for (int a = 0; a < 4; ++a) x[a] = buf[80 * k0 + l0 + 16 * a];
-  wave_sync();
-  bfly4(x);
-#pragma unroll
-  for (int q = 1; q < 4; ++q) x[q] = cmul(x[q], t.b[q - 1]);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) buf[80 * k0 + 20 * q + l0] = x[q];
-  wave_sync();
-#pragma unroll
-  for (int a = 0; a < 4; ++a) x[a] = buf[80 * k0 + 20 * k1 + l00 + 4 * a];
-  wave_sync();
-  bfly4(x);
-#pragma unroll
-  for (int q = 1; q < 4; ++q) x[q] = cmul(x[q], t.c[q - 1]);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) buf[80 * k0 + 20 * k1 + 4 * l00 + (q ^ l00)] = x[q];
-  wave_sync();
-#pragma unroll
-  for (int a = 0; a < 4; ++a) x[a] = buf[80 * k0 + 20 * k1 + 4 * a + (l00 ^ a)];      // (this lane's k2 = lane & 3)
-  wave_sync();
-  bfly4(x);
-  const int kb = k0 + 4 * k1 + 16 * l00;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) buf[nat(kb + 64 * q)] = x[q];
-  wave_sync();
-}
+static_assert(kImage == kWaveImage, "the LDS image of a wave is the one stft_wave.hpp addresses");
 
 }  // namespace
 
@@ -141,11 +78,7 @@ __global__ __launch_bounds__(64 * kWaves) void stft_block_kernel(const float* __
   float2* buf = image[wave];
   const Twiddles t = load_twiddles(tw, lane);
   float2 w[4], ws[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    w[a] = reinterpret_cast<const float2*>(win)[lane + 64 * a];              // taps 2 l + 128 a, + 1
-    ws[a] = tw[kTwS + 2 * lane + 1 + (a & 1) + 128 * (a >> 1)];               // W512^k of this lane's four bins
-  }
+  load_analysis_regs(win, tw, lane, w, ws);
   const size_t row0 = static_cast<size_t>(u) * n_hops;
   const float2* prev = reinterpret_cast<const float2*>(f0 == 0 ? tail_in + static_cast<size_t>(u) * H : pcm + (row0 + f0 - 1) * H);
   float2 p0 = prev[lane], p1 = prev[lane + 64];
@@ -158,26 +91,9 @@ __global__ __launch_bounds__(64 * kWaves) void stft_block_kernel(const float* __
       const float2* nxt = reinterpret_cast<const float2*>(pcm + (row0 + f + 1) * H);
       n0 = nxt[lane]; n1 = nxt[lane + 64];
     }
-    float2 x[4];
-    x[0] = make_float2(p0.x * w[0].x, p0.y * w[0].y);
-    x[1] = make_float2(p1.x * w[1].x, p1.y * w[1].y);
-    x[2] = make_float2(c0.x * w[2].x, c0.y * w[2].y);
-    x[3] = make_float2(c1.x * w[3].x, c1.y * w[3].y);
-    fft256(x, buf, t, lane);
     float m[4];
-    float2 rot[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 2 * lane + 1 + (i & 1) + 128 * (i >> 1);                   // bins 1..256
-      const float2 zk = buf[nat(k & 255)], zm = buf[nat(256 - k)];
-      const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-      const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-      const float2 wo = cmul(o, ws[i]);
-      const float xr = e.x + wo.x, xi = e.y + wo.y;
-      m[i] = sqrtf(xr * xr + xi * xi);
-      rot[i] = m[i] > 0.f ? make_float2(xr / m[i], xi / m[i]) : make_float2(1.f, 0.f);
-    }
-    const float2 z0 = buf[0];
+    float2 rot[4], dc;
+    analyse_frame(p0, p1, c0, c1, w, ws, t, buf, lane, m, rot, dc);
     const size_t row = row0 + f;
     float2* mrow = reinterpret_cast<float2*>(mag + row * H);
     mrow[lane] = make_float2(m[0], m[1]);
@@ -185,10 +101,7 @@ __global__ __launch_bounds__(64 * kWaves) void stft_block_kernel(const float* __
     float2* prow = ph + row * (H + 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) prow[2 * lane + 1 + (i & 1) + 128 * (i >> 1)] = rot[i];
-    if (lane == 0) {                                                           // bin 0 is real: X[0] = Re Z[0] + Im Z[0]
-      const float x0 = z0.x + z0.y;
-      prow[0] = make_float2(x0 < 0.f ? -1.f : 1.f, 0.f);
-    }
+    if (lane == 0) prow[0] = dc;
     wave_sync();                                                               // (the reads above come before the next frame's writes)
     p0 = c0; p1 = c1;
     c0 = n0; c1 = n1;
@@ -211,13 +124,7 @@ __global__ __launch_bounds__(64 * kWaves) void istft_block_kernel(const float* _
   float2* buf = image[wave];
   const Twiddles t = load_twiddles(tw, lane);
   float2 iw[4], ws[4];
-  const float scale = 1.0f / static_cast<float>(NUTLS_FRAME_LEN);
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    iw[a] = reinterpret_cast<const float2*>(inv_win)[lane + 64 * a];
-    ws[a] = tw[kTwS + lane + 64 * a];                                          // W512^k, k = l + 64 a (used conjugated)
-    ws[a].y = -ws[a].y;
-  }
+  load_synthesis_regs(inv_win, tw, lane, iw, ws);
   const size_t row0 = static_cast<size_t>(u) * n_hops;
   float2 carry0 = make_float2(0.f, 0.f), carry1 = carry0;
   if (o0 == 0) {
@@ -230,34 +137,8 @@ __global__ __launch_bounds__(64 * kWaves) void istft_block_kernel(const float* _
     const size_t row = row0 + f;
     const float2* erow = reinterpret_cast<const float2*>(est + row * H);
     const float2* prow = ph + row * (H + 1);
-    const float2 e0 = erow[lane], e1 = erow[lane + 64];                        // bins 2 l + 1, 2 l + 2 (+ 128)
-    const float es[4] = {e0.x, e0.y, e1.x, e1.y};
-    // Hermitian spectrum: bins 0..256 given, the rest mirrored; the imaginary parts of bins 0 and 256 are ignored
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = 2 * lane + 1 + (i & 1) + 128 * (i >> 1);
-      const float2 r = prow[k];
-      buf[k == 256 ? 256 : spec(k)] = make_float2(es[i] * r.x, k == 256 ? 0.f : es[i] * r.y);
-    }
-    if (lane == 0) buf[0] = make_float2(dc_edge ? e0.x * prow[0].x : 0.f, 0.f);
-    wave_sync();
-    float2 x[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int k = lane + 64 * a;
-      const float2 yk = buf[spec(k)], ym = buf[k == 0 ? 256 : spec(256 - k)];
-      const float2 e = make_float2(yk.x + ym.x, yk.y - ym.y);
-      const float2 o = cmul(make_float2(yk.x - ym.x, yk.y + ym.y), ws[a]);
-      x[a] = make_float2(e.y + o.x, e.x - o.y);                                // Z = E + i O, re / im swapped: the inverse transform
-    }
-    wave_sync();
-    fft256(x, buf, t, lane);
     float2 v[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const float2 z = buf[nat(lane + 64 * a)];                                // (swapped back: .y = sample 2 n, .x = sample 2 n + 1)
-      v[a] = make_float2(z.y * scale * iw[a].x, z.x * scale * iw[a].y);
-    }
+    synthesise_frame(erow, prow, dc_edge, iw, ws, t, buf, lane, v);
     if (f >= o0) {
       float2* orow = reinterpret_cast<float2*>(pcm_out + row * H);
       orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);

@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "nutls_set_ctfa_mode", "nutls_fused_plan_num_ops", "nutls_fused_plan_op_info", "nutls_create_plan",
     "nutls_enhance_block", "nutls_enhance_block_host", "nutls_stft_block", "nutls_istft_block",
     "nutls_step_active", "nutls_step_host_active", "nutls_enhance_hop_active", "nutls_enhance_hop_host_active",
+    "nutls_set_hop_fusion", "nutls_launches_per_hop",
 )
 
 
@@ -113,6 +114,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_step_host_active.argtypes = [c.c_void_p, fp, fp, c.c_void_p]
         lib.nutls_enhance_hop_active.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p]
         lib.nutls_enhance_hop_host_active.argtypes = [c.c_void_p, fp, fp, c.c_void_p, c.c_int]
+    if not dev_lib or hasattr(lib, "nutls_set_hop_fusion"):
+        lib.nutls_set_hop_fusion.argtypes = [c.c_void_p, c.c_int]
+        lib.nutls_launches_per_hop.argtypes = [c.c_void_p]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -182,7 +186,7 @@ class NutlsEngine:
     VARIANTS = {"lstm": 0, "baseline": 1}
 
     def __init__(self, weights=None, batch: int = 1, device: int = 0, mode: Optional[str] = None, variant: str = "lstm",
-                 streams_per_workgroup: Optional[int] = None):
+                 streams_per_workgroup: Optional[int] = None, hop_fusion: Optional[bool] = None):
         """``mode``: "fused" (the default when the container holds int8 conv kernels, as the reference's .tflite does:
         one launch per frame, one workgroup per one / two / four streams, every op its own specialised instruction stream),
         "graph" (one kernel per layer, hipGraph replay; the default for float containers) or "launches" (one kernel per layer).
@@ -191,7 +195,9 @@ class NutlsEngine:
         ``weights.write_blob(weights.synthetic_weights("baseline"), int8_convs=True)``).
         ``streams_per_workgroup``: which plan the fused kernel runs -- None: the library's choice (a packed plan, two or four streams
         per workgroup, where its cost model finds one faster: more streams than CUs), 1 / 2 / 4: that plan (``nutls_create_plan``; a batch
-        that is not a multiple, or a variant without such a plan, raises)."""
+        that is not a multiple, or a variant without such a plan, raises).
+        ``hop_fusion``: True / False: ``set_hop_fusion`` once the mode is set (``enhance_hop`` as ONE launch instead of three; raises where the
+        handle has no hop build); None (default): the handle stays as the library created it -- off, or on under ``NUTLS_HOP_FUSION=1``."""
         self._lib = load_library()
         if variant not in self.VARIANTS:
             raise ValueError("variant must be one of %s" % sorted(self.VARIANTS))
@@ -217,6 +223,8 @@ class NutlsEngine:
                 self.set_mode("fused")
             except ValueError:
                 self.set_mode("graph")
+        if hop_fusion is not None:
+            self.set_hop_fusion(hop_fusion)
 
     # -- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -255,6 +263,18 @@ class NutlsEngine:
     @property
     def launches_per_step(self) -> int:
         return self._lib.nutls_launches_per_step(self._h)
+
+    def set_hop_fusion(self, enable: bool = True) -> None:
+        """``enhance_hop`` as ONE launch: STFT analysis and inverse STFT / overlap-add run inside the fused step kernel (its hop build) instead
+        of in a launch each in front of and behind it (``nutls_set_hop_fusion``).  Same per-stream state and buffers: it may be switched
+        between any two hops.  LSTM variant, fused mode, one- or two-stream plan; raises ValueError elsewhere, and while it is on
+        ``set_mode("graph" / "launches")``, ``debug_trace()`` and the profiling calls raise instead of quietly going back to three launches."""
+        _check(self._lib, self._lib.nutls_set_hop_fusion(self._h, 1 if enable else 0))
+
+    @property
+    def launches_per_hop(self) -> int:
+        """Launches one ``enhance_hop`` issues: 3 (analysis, step, synthesis), or 1 with hop fusion on."""
+        return int(self._lib.nutls_launches_per_hop(self._h))
 
     # -- the hot path ----------------------------------------------------------------------
     def _host_mask(self, active) -> np.ndarray:
@@ -333,7 +353,12 @@ class NutlsEngine:
             x = np.ascontiguousarray(pcm, dtype=np.float32)
             if x.shape != (self.batch, 256):
                 raise ValueError("pcm must be [%d,256], got %s" % (self.batch, x.shape))
-            o = np.empty_like(x)
+            if out is None:
+                o = np.empty_like(x)
+            else:       # (arrays from ``host_alloc`` for both ``pcm`` and ``out``: with hop fusion on the kernel works on them over the link, no copies)
+                o = out
+                if not (isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous and o.shape == x.shape):
+                    raise ValueError("out must be a contiguous float32 numpy array of pcm's shape")
             if active is not None:
                 a = self._host_mask(active)
                 _check(self._lib, self._lib.nutls_enhance_hop_host_active(self._h, _fptr(x), _fptr(o), a.ctypes.data, self._DC[dc_mode]))

@@ -152,11 +152,14 @@ def real_time_speech_enhancer(noisy_speech: np.ndarray, runner: Callable[..., Di
     return wave, seconds
 
 
-def enhance_batch_on_device(noisy: np.ndarray, engine, dc_mode: str = "edge") -> np.ndarray:
+def enhance_batch_on_device(noisy: np.ndarray, engine, dc_mode: str = "edge", hop_fusion=None) -> np.ndarray:
     """The same loop with the STFT / inverse STFT on the GPU too: ``noisy [B, N]`` (one utterance per stream,
     equal lengths) -> enhanced ``[B, N]`` in the alignment of :func:`real_time_speech_enhancer` (whose first
     256 output samples are dropped, interpreter_proposed.py:368).  Only PCM hops cross the host boundary:
-    ``engine.enhance_hop`` = ``nutls_enhance_hop_host`` of the C ABI."""
+    ``engine.enhance_hop`` = ``nutls_enhance_hop_host`` of the C ABI.  ``hop_fusion``: True / False: ``engine.set_hop_fusion`` first (every hop
+    one launch instead of three); None: the engine as it is."""
+    if hop_fusion is not None:
+        engine.set_hop_fusion(hop_fusion)
     audio = np.asarray(noisy, np.float32)
     if audio.ndim == 1:
         audio = audio[None]
