@@ -232,6 +232,46 @@ int nutls_offline_set_pipeline(nutls_handle* h, int chunks);
 /* Same with HOST buffers (synchronises). */
 int nutls_process_block_host(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames);
 
+/* ---- Ragged blocks: per-utterance frame counts for the offline batch handles ------------------------------------
+ * nutls_process_block steps the same number of frames of every utterance; recordings never have equal lengths.  The entries below take,
+ * beside the block's row stride n_frames / n_hops (1 .. max_frames), `frames` / `hops`: [utterances] int, frames[u] in 0 .. n_frames = how
+ * many LEADING frames of utterance u are real.  Buffers keep their layouts, [utterances, n_frames, 256] and [utterances, n_hops * 256]
+ * (with counts: 16-byte aligned).  For utterance u with k = frames[u], one call
+ *   - writes rows 0 .. k-1 of mag_out / pcm_out with exactly the bits the uniform call of the same width on the same handle writes there
+ *     (the model runs the same launches at the same sizes: every layer is causal in time and utterances never mix, so a frame does not
+ *     depend on the rows behind it or on another utterance);
+ *   - writes rows k .. n_frames-1 of the output with ZEROS.  The matching input rows have no effect on any result and may hold anything,
+ *     NaN included: they are replaced by zeros on the way into the library's own input buffer (the waveform entries never read those PCM
+ *     rows and write zero magnitudes).  The caller's input buffer is never written;
+ *   - carries to the next call what belongs to frame k, not to frame n_frames: the 130 state tensors, under NUTLS_CTFA_CAUSAL32 the 31-row
+ *     time-attention history of each of the 12 stages, in the waveform entries the previous hop (hop k-1) and the overlap tail (second
+ *     half of frame k-1).  nutls_debug_get("phasor_block") rows >= k are unspecified;
+ *   - k = 0 HOLDS the utterance: everything it carries stays exactly as it was.
+ * An utterance that receives its frames in ragged calls of counts k1, k2, ... therefore produces the same concatenated result as any other
+ * cut of the same frames on a handle of the same shape; a recording that ends frees its slot with nutls_reset(h, u), and the next one
+ * joins the slot in the next block without disturbing the others.
+ *
+ * nutls_process_block_ragged / nutls_enhance_block_ragged / nutls_stft_block_ragged / nutls_istft_block_ragged: the counts are a DEVICE
+ * pointer, read by the kernels: it must stay valid and unmodified until the work queued on `stream` has run.  The host cannot see those
+ * counts (and does not synchronise to look): the kernels clamp them to 0 .. n_frames.  The _host entries take the counts in HOST memory,
+ * check them -- one outside 0 .. n_frames is NUTLS_ERR_ARG, and nothing has been touched -- and copy them themselves.
+ * frames == NULL / hops == NULL means every frame of every utterance: the call IS the entry without counts (same code path, same bits).
+ *
+ * Supported: offline handles (nutls_create_offline, nutls_create_offline_batch), both CTFA modes, every nutls_offline_set_pipeline chunk
+ * count.  A streaming handle gets NUTLS_ERR_ARG from all six (its streams run on their own clocks with nutls_step_active).
+ * Cost: a ragged block costs what the uniform block of its row stride costs -- the frames behind a count are computed and discarded;
+ * skipping them inside the layers' launches is not attempted -- plus three small copy kernels: the masked copies in and out and the
+ * per-utterance gather of the carried state (in place of the uniform call's two copies and its strided copy of the last slot; the gather
+ * moves one arena slot per utterance).  Choose the row stride as the longest count of the block. */
+int nutls_process_block_ragged(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames, void* stream);
+int nutls_process_block_ragged_host(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames);
+int nutls_enhance_block_ragged(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
+int nutls_enhance_block_ragged_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, const int* hops, int dc_mode);
+/* The two halves on their own, as nutls_stft_block / nutls_istft_block: the synthesis belongs to the last analysed block (same n_hops; pass
+ * the same counts). */
+int nutls_stft_block_ragged(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, const int* hops, void* stream);
+int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
+
 /* Library-owned device staging buffers [B,256]; stepping on them avoids the D2D copies and lets
  * the captured hipGraph run with no per-call parameter update. */
 int nutls_io_buffers(nutls_handle* h, float** mag_in, float** mag_out);

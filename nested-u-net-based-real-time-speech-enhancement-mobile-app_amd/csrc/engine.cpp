@@ -21,6 +21,7 @@
 #include "../../include/nutls.h"
 #include "nutls_internal.hpp"
 #include "fused_host.hpp"
+#include "ragged.hpp"
 
 namespace nutls {
 
@@ -164,6 +165,7 @@ struct Engine {
   std::vector<hipEvent_t> oev;          // [chunk stream][2 * kGroups]: slot g = the chunk's conv-like launches of group g are enqueued, kGroups + g = its LSTM of group g
   hipEvent_t oev_fork = nullptr;
   int ochunks = 0;                      // 0 = chosen from the block length
+  int* d_counts = nullptr;              // [outt] ints: device copy of the counts of the _host entries of the ragged block calls (nutls_process_block_ragged_host)
   std::vector<int> ogroup;              // launch index of plan_off -> group (a group ends with an LSTM)
   int next_parity = 0;   // parity the next step writes (`cur`); `prev` is read from 1 - next_parity
   int mode = 0;          // 0 plain per-layer launches, 1 per-layer hipGraph replay, 3 fused kernel (statically scheduled; both variants);
@@ -1165,21 +1167,24 @@ static int block_dc(int dc_mode, const char* who) {
   return NUTLS_OK;
 }
 
-static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_hops, hipStream_t s) {
+static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_hops, hipStream_t s, const int* hops = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
-  HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, e->outt, n_hops, s));
+  if (hops) HIP_TRY(launch_stft_block_ragged(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, hops, e->outt, n_hops, s));
+  else HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, e->outt, n_hops, s));
   e->fb_tail_par ^= 1;
   e->fb_hops = n_hops;
   return NUTLS_OK;
 }
 
-static int istft_block_launch(Engine* e, const float* mag, float* pcm_out, int n_hops, int dc_mode, hipStream_t s) {
+static int istft_block_launch(Engine* e, const float* mag, float* pcm_out, int n_hops, int dc_mode, hipStream_t s, const int* hops = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
   if (n_hops != e->fb_hops) return fail(NUTLS_ERR_ARG, "nutls_istft_block: n_hops differs from the block the phasors inside the handle belong to (nutls_stft_block first)");
-  HIP_TRY(launch_istft_block(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
-                             dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->outt, n_hops, s));
+  if (hops) HIP_TRY(launch_istft_block_ragged(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
+                                              dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
+  else HIP_TRY(launch_istft_block(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
+                                  dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->outt, n_hops, s));
   e->fb_ola_par ^= 1;
   return NUTLS_OK;
 }
@@ -1488,23 +1493,33 @@ int nutls_set_ctfa_mode(nutls_handle* h, int mode) {
   return NUTLS_OK;
 }
 
-int nutls_process_block(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, void* stream) {
-  if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_process_block: null pointer");
+// One block of n_frames frames of every utterance.  frames == nullptr: nutls_process_block.  frames != nullptr (DEVICE, [utterances]): the
+// ragged block of nutls_process_block_ragged -- every layer is causal in time and utterances never mix, so the block itself runs exactly as
+// the uniform one of width n_frames (same launches, same sizes); the rows behind an utterance's count are zeros on the way in and out, and the
+// commit behind the block takes what is carried from frame frames[u] instead of frame n_frames.  in_place: the caller (nutls_enhance_block_ragged)
+// has staged the library's own buffers -- its analysis wrote the zero rows, its synthesis reads no row behind a count.
+static int process_block_impl(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames, bool in_place, void* stream,
+                              const char* who) {
+  if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
   Engine* e = &h->eng;
-  if (!e->offline) return fail(NUTLS_ERR_ARG, "nutls_process_block: not an offline handle (nutls_create_offline)");
-  if (n_frames < 1 || n_frames > e->offline) return fail(NUTLS_ERR_ARG, "nutls_process_block: n_frames out of range");
+  if (!e->offline) return fail(NUTLS_ERR_ARG, std::string(who) + ": not an offline handle (nutls_create_offline)");
+  if (n_frames < 1 || n_frames > e->offline) return fail(NUTLS_ERR_ARG, std::string(who) + ": n_frames out of range");
+  if (frames && ((reinterpret_cast<uintptr_t>(mag_in) | reinterpret_cast<uintptr_t>(mag_out)) & 15))
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": with frame counts the magnitude buffers must be 16-byte aligned");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int U = e->outt;
   const size_t bytes = static_cast<size_t>(U) * n_frames * NUTLS_BINS * sizeof(float);
-  if (mag_in != e->io_in) HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyDeviceToDevice, s));
+  if (frames) {
+    if (!in_place) HIP_TRY(launch_ragged_rows(mag_in, e->io_in, frames, U, n_frames, s));
+  } else if (mag_in != e->io_in) HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyDeviceToDevice, s));
   int C = e->ochunks;
   if (C == 0) C = n_frames >= 768 ? 3 : n_frames >= 256 ? 2 : 1;      // (four compute queues are served at a time: chunk 0 rides on the caller's stream, three chunks = three queues)
   C = std::max(1, std::min({C, static_cast<int>(Engine::kMaxChunks), n_frames}));
   // (several utterances: every launch runs all of them -- their 13 scans side by side on their own wavefronts, the small layers U times fuller;
   //  the chunks cut the frames of every utterance alike)
   if (C == 1) {
-    int rc = launch_block_range(e, 0, e->plan_off.size(), 0, n_frames, true, s);
+    int rc = launch_block_range(e, 0, e->plan_off.size(), 0, n_frames, frames == nullptr, s);      // (ragged: the history is rolled by the commit below)
     if (rc) return rc;
   } else {
     // chunk c, group g (= the layers up to and including bottleneck g) starts when chunk c-1 has finished group g: then
@@ -1551,11 +1566,20 @@ int nutls_process_block(nutls_handle* h, const float* mag_in, float* mag_out, in
       if (hipEventRecord(done, cs(c)) == hipSuccess) (void)hipStreamWaitEvent(s, done, 0);
     }
     if (rc) return rc;
-    if (e->ctfa_causal)
+    if (e->ctfa_causal && !frames)
       for (int k = 0; k < 12; ++k) {
         hipError_t err = launch_ctfa_hist_roll(e->ta_hist + static_cast<size_t>(k) * (31 + e->offline) * 64, n_frames, s, U, static_cast<long long>(12) * (31 + e->offline) * 64);
         if (err != hipSuccess) return fail(NUTLS_ERR_HIP, std::string("time-attention history roll: ") + hipGetErrorString(err));
       }
+  }
+  if (frames) {
+    // stage-out and commit, behind the join of the chunk streams: utterance u's carried state is the slot of its frame frames[u], its
+    // time-attention history the 31 rows in front of that frame's; frames[u] = 0 moves nothing
+    if (!in_place) HIP_TRY(launch_ragged_rows(e->io_out, mag_out, frames, U, n_frames, s));
+    if (e->ctfa_causal) HIP_TRY(launch_ragged_hist_roll(e->ta_hist, 31 + e->offline, frames, U, n_frames, s));
+    HIP_TRY(launch_ragged_state_gather(e->arena, static_cast<long long>(e->sstride), e->offline + 1, frames, U, n_frames, s));
+    e->steps += n_frames;
+    return NUTLS_OK;
   }
   if (mag_out != e->io_out) HIP_TRY(hipMemcpyAsync(mag_out, e->io_out, bytes, hipMemcpyDeviceToDevice, s));
   // the last frame's slot of every utterance becomes its carried state of the next block
@@ -1564,6 +1588,46 @@ int nutls_process_block(nutls_handle* h, const float* mag_in, float* mag_out, in
     HIP_TRY(hipMemcpy2DAsync(e->arena, pitch, e->arena + static_cast<size_t>(n_frames) * e->sstride, pitch, e->sstride * sizeof(float), U, hipMemcpyDeviceToDevice, s));
   }
   e->steps += n_frames;
+  return NUTLS_OK;
+}
+
+int nutls_process_block(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, void* stream) {
+  return process_block_impl(h, mag_in, mag_out, n_frames, nullptr, false, stream, "nutls_process_block");
+}
+
+int nutls_process_block_ragged(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames, void* stream) {
+  return process_block_impl(h, mag_in, mag_out, n_frames, frames, false, stream, frames ? "nutls_process_block_ragged" : "nutls_process_block");
+}
+
+// The counts of a _host entry: checked (nothing is touched when one is out of range), then copied to the handle's device buffer on the
+// library's stream, in front of the work that reads them.
+static int upload_counts(Engine* e, const int* counts, int n, const char* who) {
+  for (int u = 0; u < e->outt; ++u)
+    if (counts[u] < 0 || counts[u] > n)
+      return fail(NUTLS_ERR_ARG, std::string(who) + ": count " + std::to_string(counts[u]) + " of utterance " + std::to_string(u) + " is outside 0 .. " + std::to_string(n));
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->d_counts) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, static_cast<size_t>(e->outt) * sizeof(int)));
+    e->allocs.push_back(p);
+    e->d_counts = static_cast<int*>(p);
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_counts, counts, static_cast<size_t>(e->outt) * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  return NUTLS_OK;
+}
+
+int nutls_process_block_ragged_host(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames) {
+  if (!frames) return nutls_process_block_host(h, mag_in, mag_out, n_frames);
+  if (!h || !mag_in || !mag_out) return fail(NUTLS_ERR_ARG, "nutls_process_block_ragged_host: null pointer");
+  Engine* e = &h->eng;
+  if (!e->offline || n_frames < 1 || n_frames > e->offline) return fail(NUTLS_ERR_ARG, "nutls_process_block_ragged_host: not an offline handle or n_frames out of range");
+  if (int rc = upload_counts(e, frames, n_frames, "nutls_process_block_ragged_host")) return rc;
+  const size_t bytes = static_cast<size_t>(e->outt) * n_frames * NUTLS_BINS * sizeof(float);
+  // (the rows behind the counts cross the link too and are zeroed on the device: the stage-in kernel runs in place on the library's buffer)
+  HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = process_block_impl(h, e->io_in, e->io_out, n_frames, e->d_counts, false, e->stream, "nutls_process_block_ragged_host")) return rc;
+  HIP_TRY(hipMemcpyAsync(mag_out, e->io_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return NUTLS_OK;
 }
 
@@ -1992,6 +2056,51 @@ int nutls_enhance_block_host(nutls_handle* h, const float* pcm_in, float* pcm_ou
   const size_t bytes = static_cast<size_t>(e->outt) * n_hops * NUTLS_FRAME_STEP * sizeof(float);
   HIP_TRY(hipMemcpyAsync(e->fb_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
   if (int rc = nutls_enhance_block(h, e->fb_pcm_in, e->fb_pcm_out, n_hops, dc_mode, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->fb_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return NUTLS_OK;
+}
+
+// ---- ragged waveform blocks: hops [utterances] of int, utterance u has hops[u] real hops in a block whose row stride is n_hops (nutls.h) ----
+int nutls_stft_block_ragged(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, const int* hops, void* stream) {
+  if (!hops) return nutls_stft_block(h, pcm_in, mag, n_hops, stream);
+  if (int rc = block_args(h, pcm_in && mag, n_hops, "nutls_stft_block_ragged")) return rc;
+  return stft_block_launch(&h->eng, pcm_in, mag, n_hops, static_cast<hipStream_t>(stream), hops);
+}
+
+int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  if (!hops) return nutls_istft_block(h, mag, pcm_out, n_hops, dc_mode, stream);
+  if (int rc = block_args(h, mag && pcm_out, n_hops, "nutls_istft_block_ragged")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_istft_block_ragged")) return rc;
+  return istft_block_launch(&h->eng, mag, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream), hops);
+}
+
+int nutls_enhance_block_ragged(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  if (!hops) return nutls_enhance_block(h, pcm_in, pcm_out, n_hops, dc_mode, stream);
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_ragged")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_enhance_block_ragged")) return rc;
+  Engine* e = &h->eng;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the analysis writes zero magnitudes behind the counts and the synthesis reads no row there: the block runs in place on the library's buffers
+  if (int rc = stft_block_launch(e, pcm_in, e->io_in, n_hops, s, hops)) return rc;
+  if (int rc = process_block_impl(h, e->io_in, e->io_out, n_hops, hops, true, stream, "nutls_enhance_block_ragged")) return rc;
+  return istft_block_launch(e, e->io_out, pcm_out, n_hops, dc_mode, s, hops);
+}
+
+int nutls_enhance_block_ragged_host(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, const int* hops, int dc_mode) {
+  if (!hops) return nutls_enhance_block_host(h, pcm_in, pcm_out, n_hops, dc_mode);
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_ragged_host")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_enhance_block_ragged_host")) return rc;
+  Engine* e = &h->eng;
+  if (int rc = upload_counts(e, hops, n_hops, "nutls_enhance_block_ragged_host")) return rc;
+  if (!e->fb_pcm_in) {
+    const size_t n = static_cast<size_t>(e->outt) * e->offline * NUTLS_FRAME_STEP;
+    if (int rc = dev_alloc(e, n, &e->fb_pcm_out, false)) return rc;
+    if (int rc = dev_alloc(e, n, &e->fb_pcm_in, false)) return rc;
+  }
+  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * NUTLS_FRAME_STEP * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(e->fb_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = nutls_enhance_block_ragged(h, e->fb_pcm_in, e->fb_pcm_out, n_hops, e->d_counts, dc_mode, e->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(pcm_out, e->fb_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return NUTLS_OK;

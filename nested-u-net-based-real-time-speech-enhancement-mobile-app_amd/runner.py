@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "nutls_enhance_block", "nutls_enhance_block_host", "nutls_stft_block", "nutls_istft_block",
     "nutls_step_active", "nutls_step_host_active", "nutls_enhance_hop_active", "nutls_enhance_hop_host_active",
     "nutls_set_hop_fusion", "nutls_launches_per_hop",
+    "nutls_process_block_ragged", "nutls_process_block_ragged_host", "nutls_enhance_block_ragged", "nutls_enhance_block_ragged_host",
+    "nutls_stft_block_ragged", "nutls_istft_block_ragged",
 )
 
 
@@ -117,6 +119,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not dev_lib or hasattr(lib, "nutls_set_hop_fusion"):
         lib.nutls_set_hop_fusion.argtypes = [c.c_void_p, c.c_int]
         lib.nutls_launches_per_hop.argtypes = [c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_process_block_ragged"):
+        ip = c.POINTER(c.c_int)
+        lib.nutls_process_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
+        lib.nutls_process_block_ragged_host.argtypes = [c.c_void_p, fp, fp, c.c_int, ip]
+        lib.nutls_enhance_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
+        lib.nutls_enhance_block_ragged_host.argtypes = [c.c_void_p, fp, fp, c.c_int, ip, c.c_int]
+        lib.nutls_stft_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
+        lib.nutls_istft_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -577,6 +587,41 @@ class NutlsRunner:
         return res
 
 
+def plan_ragged_blocks(lengths_in_hops, utterances: int, max_frames: int):
+    """The schedule of :meth:`NutlsOffline.enhance_many`, a pure function: ``lengths_in_hops[i]`` hops (or frames) of item ``i`` through
+    ``utterances`` slots in blocks of at most ``max_frames`` per slot.  Returns a list of blocks, each a list of
+    ``(slot, item, first_hop, count, reset_before)`` in slot order: the block takes hops ``first_hop .. first_hop + count - 1`` of ``item`` in
+    ``slot``; ``reset_before`` marks the first block of an item in its slot (the slot is reset in front of it).  An item stays in its slot
+    until it ends and continues there block after block; a slot whose item has ended takes the next item of the queue in the next block;
+    a slot with nothing to do is absent from the block (count 0: held).  The queue is served longest first, so that the blocks at the end of
+    the run, which the last items have to themselves, are short ones.  Items of length 0 take no slot."""
+    lengths = [int(n) for n in lengths_in_hops]
+    utterances, max_frames = int(utterances), int(max_frames)
+    if utterances < 1 or max_frames < 1 or any(n < 0 for n in lengths):
+        raise ValueError("plan_ragged_blocks: utterances and max_frames must be >= 1, lengths >= 0")
+    queue = sorted((i for i, n in enumerate(lengths) if n > 0), key=lambda i: (-lengths[i], i))
+    slots = [None] * utterances          # per slot: [item, next hop]
+    blocks, q = [], 0
+    while True:
+        for u in range(utterances):
+            if slots[u] is None and q < len(queue):
+                slots[u] = [queue[q], 0]
+                q += 1
+        block = []
+        for u, cur in enumerate(slots):
+            if cur is None:
+                continue
+            item, first = cur
+            count = min(max_frames, lengths[item] - first)
+            block.append((u, item, first, count, first == 0))
+            cur[1] = first + count
+            if cur[1] == lengths[item]:
+                slots[u] = None
+        if not block:
+            return blocks
+        blocks.append(block)
+
+
 class NutlsOffline:
     """Offline / block mode: ``utterances`` independent utterances, up to ``max_frames`` consecutive frames of each
     per call -- every conv-like layer runs once per block over all frames of all utterances (the frame index takes the place of
@@ -626,9 +671,32 @@ class NutlsOffline:
             out[:, a:a + blk.shape[1]] = o
         return out if batched else out[0]
 
-    def process_block_device(self, mag, out=None):
+    def _device_counts(self, counts, n: int, like, name: str):
+        """Per-utterance counts of a device call -> device pointer.  An int32 CUDA tensor ``[utterances]`` is handed to the kernels as it is
+        (it must stay unmodified until the queued work has run; the kernels clamp its values to ``0 .. n``); anything else array-like is
+        checked here (``0 .. n``) and copied to the device."""
+        import torch
+        if torch.is_tensor(counts) and counts.is_cuda:
+            if counts.dtype != torch.int32 or not counts.is_contiguous() or tuple(counts.shape) != (self.utterances,) or counts.device != like.device:
+                raise ValueError("%s must be a contiguous int32 CUDA tensor of length %d on the block's device" % (name, self.utterances))
+            return counts.data_ptr()
+        host = self._host_counts(counts, n, name)
+        self._counts_dev = torch.from_numpy(host).to(like.device)      # (kept until the next call: the queued kernels read it)
+        return self._counts_dev.data_ptr()
+
+    def _host_counts(self, counts, n: int, name: str) -> np.ndarray:
+        a = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+        if a.shape != (self.utterances,) or a.dtype.kind not in "iu":
+            raise ValueError("%s must be %d integers (one count per utterance), got %s %s" % (name, self.utterances, a.dtype, a.shape))
+        if a.size and (int(a.min()) < 0 or int(a.max()) > n):
+            raise ValueError("%s must lie in 0 .. %d (the block's row stride), got %s" % (name, n, a.tolist()))
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def process_block_device(self, mag, out=None, frames=None):
         """One block on device tensors: ``mag [n,256]`` (one utterance) or ``[utterances,n,256]`` float32 CUDA tensor, n <= max_frames;
-        asynchronous on the current torch stream."""
+        asynchronous on the current torch stream.  ``frames`` (``nutls_process_block_ragged``): how many leading frames of every utterance
+        are real -- an int32 CUDA tensor ``[utterances]`` or anything array-like; rows behind a count are zeros in ``out``, have no effect
+        as input, and the utterance carries on from its own last real frame (count 0: the utterance is held).  ``None``: all ``n`` of all."""
         import torch
         if not (torch.is_tensor(mag) and mag.is_cuda and mag.dtype == torch.float32 and mag.is_contiguous()):
             raise ValueError("mag must be a contiguous float32 CUDA tensor")
@@ -640,7 +708,11 @@ class NutlsOffline:
         if out is None:
             out = torch.empty_like(mag)
         stream = torch.cuda.current_stream(mag.device).cuda_stream
-        _check(self._lib, self._lib.nutls_process_block(self._h, mag.data_ptr(), out.data_ptr(), int(shape[-2]), stream))
+        if frames is None:
+            _check(self._lib, self._lib.nutls_process_block(self._h, mag.data_ptr(), out.data_ptr(), int(shape[-2]), stream))
+        else:
+            cnt = self._device_counts(frames, int(shape[-2]), mag, "frames")
+            _check(self._lib, self._lib.nutls_process_block_ragged(self._h, mag.data_ptr(), out.data_ptr(), int(shape[-2]), cnt, stream))
         return out
 
     # -- waveform block mode: STFT / inverse STFT + overlap-add of whole blocks on the device (csrc/stft_block.hip) --------------
@@ -676,10 +748,12 @@ class NutlsOffline:
                 name, "%d," % self.utterances if self.utterances > 1 else "", self.max_frames, T.N_BINS, shape))
         return shape[-2]
 
-    def enhance_block_device(self, pcm, out=None, dc_mode: str = "edge"):
+    def enhance_block_device(self, pcm, out=None, dc_mode: str = "edge", hops=None):
         """One block of PCM on device tensors: ``pcm [n_hops*256]`` (one utterance) or ``[utterances, n_hops*256]`` float32 CUDA tensor,
         n_hops <= max_frames -> the enhanced PCM of the same shape, one hop late like ``NutlsEngine.enhance_hop``
-        (``nutls_enhance_block``: analysis, ``process_block``, synthesis); asynchronous on the current torch stream."""
+        (``nutls_enhance_block``: analysis, ``process_block``, synthesis); asynchronous on the current torch stream.
+        ``hops``: per-utterance counts as ``frames`` of :meth:`process_block_device` (``nutls_enhance_block_ragged``); the PCM rows behind a
+        count are never read, the matching rows of ``out`` are zeros."""
         import torch
         dc = self._dc(dc_mode)
         n = self._pcm_hops(pcm)
@@ -688,13 +762,16 @@ class NutlsOffline:
         elif self._cuda_f32(out, "out").shape != pcm.shape or out.device != pcm.device:
             raise ValueError("out must have pcm's shape and device")
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        _check(self._lib, self._lib.nutls_enhance_block(self._h, pcm.data_ptr(), out.data_ptr(), n, dc, stream))
+        if hops is None:
+            _check(self._lib, self._lib.nutls_enhance_block(self._h, pcm.data_ptr(), out.data_ptr(), n, dc, stream))
+        else:
+            _check(self._lib, self._lib.nutls_enhance_block_ragged(self._h, pcm.data_ptr(), out.data_ptr(), n, self._device_counts(hops, n, pcm, "hops"), dc, stream))
         return out
 
-    def stft_block_device(self, pcm, out=None):
+    def stft_block_device(self, pcm, out=None, hops=None):
         """Analysis half only: ``pcm`` as in :meth:`enhance_block_device` -> magnitudes of bins 1..256, ``[n_hops,256]`` /
         ``[utterances,n_hops,256]`` (what :meth:`process_block_device` takes); the phase stays inside the handle
-        (``debug_get("phasor_block", (n_hops, 257, 2))``)."""
+        (``debug_get("phasor_block", (n_hops, 257, 2))``).  ``hops``: per-utterance counts (``nutls_stft_block_ragged``)."""
         import torch
         n = self._pcm_hops(pcm)
         shape = tuple(pcm.shape[:-1]) + (n, T.N_BINS)
@@ -703,12 +780,16 @@ class NutlsOffline:
         elif tuple(self._cuda_f32(out, "out").shape) != shape or out.device != pcm.device:
             raise ValueError("out must be %s on pcm's device" % (shape,))
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        _check(self._lib, self._lib.nutls_stft_block(self._h, pcm.data_ptr(), out.data_ptr(), n, stream))
+        if hops is None:
+            _check(self._lib, self._lib.nutls_stft_block(self._h, pcm.data_ptr(), out.data_ptr(), n, stream))
+        else:
+            _check(self._lib, self._lib.nutls_stft_block_ragged(self._h, pcm.data_ptr(), out.data_ptr(), n, self._device_counts(hops, n, pcm, "hops"), stream))
         return out
 
-    def istft_block_device(self, mag, out=None, dc_mode: str = "edge"):
+    def istft_block_device(self, mag, out=None, dc_mode: str = "edge", hops=None):
         """Synthesis half only: magnitudes ``[n_hops,256]`` / ``[utterances,n_hops,256]`` with the phase of the last
-        :meth:`stft_block_device` of the same ``n_hops`` -> PCM ``[n_hops*256]`` / ``[utterances,n_hops*256]``, overlap-added."""
+        :meth:`stft_block_device` of the same ``n_hops`` -> PCM ``[n_hops*256]`` / ``[utterances,n_hops*256]``, overlap-added.
+        ``hops``: the counts that analysis was given (``nutls_istft_block_ragged``)."""
         import torch
         dc = self._dc(dc_mode)
         n = self._mag_hops(mag)
@@ -718,7 +799,10 @@ class NutlsOffline:
         elif tuple(self._cuda_f32(out, "out").shape) != shape or out.device != mag.device:
             raise ValueError("out must be %s on mag's device" % (shape,))
         stream = torch.cuda.current_stream(mag.device).cuda_stream
-        _check(self._lib, self._lib.nutls_istft_block(self._h, mag.data_ptr(), out.data_ptr(), n, dc, stream))
+        if hops is None:
+            _check(self._lib, self._lib.nutls_istft_block(self._h, mag.data_ptr(), out.data_ptr(), n, dc, stream))
+        else:
+            _check(self._lib, self._lib.nutls_istft_block_ragged(self._h, mag.data_ptr(), out.data_ptr(), n, self._device_counts(hops, n, mag, "hops"), dc, stream))
         return out
 
     def enhance_block_host(self, pcm: np.ndarray, out: Optional[np.ndarray] = None, dc_mode: str = "edge") -> np.ndarray:
@@ -756,6 +840,77 @@ class NutlsOffline:
             out[:, a * 256:b * 256] = self.enhance_block_host(blk, None, dc_mode)
         out = out[:, 256:]
         return out if batched else out[0]
+
+    # -- ragged blocks: per-utterance counts (nutls_process_block_ragged_host / nutls_enhance_block_ragged_host) ---------------------
+    def _ragged_host(self, entry, chunks, unit: int, *tail):
+        """One ragged block through a ``_host`` entry.  ``chunks[u]``: utterance u's piece of the block, ``k_u`` frames ``[k_u,256]``
+        (``unit`` 1) or ``k_u`` hops of PCM ``[k_u * 256]`` (``unit`` 256), k_u <= max_frames and at least one > 0; the row stride of the
+        block is the longest count.  Returns each utterance's piece of the result."""
+        counts = np.array([c.shape[0] // unit for c in chunks], np.int32)
+        n = int(counts.max())
+        blk = np.zeros((self.utterances, n * unit) + chunks[0].shape[1:], np.float32)
+        for u, c in enumerate(chunks):
+            blk[u, :c.shape[0]] = c
+        out = np.empty_like(blk)
+        _check(self._lib, entry(self._h, _fptr(blk), _fptr(out), n, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), *tail))
+        return [out[u, :c.shape[0]] for u, c in enumerate(chunks)]
+
+    def _ragged_list(self, items, what: str, ndim: int):
+        items = [np.ascontiguousarray(x, dtype=np.float32) for x in items]
+        if len(items) != self.utterances or any(x.ndim != ndim or (ndim == 2 and x.shape[1] != T.N_BINS) for x in items):
+            raise ValueError("%s must be a list of %d arrays %s (one per utterance, any lengths)" % (
+                what, self.utterances, "[N,%d]" % T.N_BINS if ndim == 2 else "[N]"))
+        return items
+
+    def process_ragged(self, mags_list) -> List[np.ndarray]:
+        """``utterances`` magnitude arrays ``[N_u,256]`` of ANY lengths (0 included) -> the enhanced magnitudes, same lengths.  Blocks of
+        ``max_frames``: utterance u takes ``min(max_frames, remaining)`` frames of each (``nutls_process_block_ragged_host``), an
+        utterance that has ended is held.  State carries on into the next call until :meth:`reset` / :meth:`reset_utterance`."""
+        mags = self._ragged_list(mags_list, "mags_list", 2)
+        outs = [np.empty_like(m) for m in mags]
+        for a in range(0, max([len(m) for m in mags] + [0]), self.max_frames):
+            got = self._ragged_host(self._lib.nutls_process_block_ragged_host, [m[a:a + self.max_frames] for m in mags], 1)
+            for o, g in zip(outs, got):
+                o[a:a + len(g)] = g
+        return outs
+
+    def enhance_ragged(self, waves_list, dc_mode: str = "edge") -> List[np.ndarray]:
+        """``utterances`` waveforms ``[N_u]`` of ANY lengths -> the enhanced waveforms, same lengths, each in the alignment of
+        :meth:`enhance` (``(N_u - 256) // 256`` hops, the first output hop dropped); blocks of ``max_frames`` hops through
+        ``nutls_enhance_block_ragged_host``.  Previous hop, overlap tail and model state of every utterance carry on until :meth:`reset`."""
+        dc = self._dc(dc_mode)
+        waves = self._ragged_list(waves_list, "waves_list", 1)
+        hops = [max(0, (len(w) - 256) // 256) for w in waves]
+        outs = [np.zeros(len(w) + 256, np.float64) for w in waves]
+        for a in range(0, max(hops), self.max_frames):
+            chunks = [w[a * 256:min(h, a + self.max_frames) * 256] for w, h in zip(waves, hops)]
+            got = self._ragged_host(self._lib.nutls_enhance_block_ragged_host, chunks, 256, dc)
+            for o, g in zip(outs, got):
+                o[a * 256:a * 256 + len(g)] = g
+        return [o[256:] for o in outs]
+
+    def enhance_many(self, waves, dc_mode: str = "edge") -> List[np.ndarray]:
+        """ANY NUMBER of recordings ``[N_i]`` of any lengths through the handle's ``utterances`` slots (:func:`plan_ragged_blocks`: longest
+        first; a recording longer than one block continues in its slot, a slot whose recording has ended is reset and takes the next one of
+        the queue in the next block, the other slots are not disturbed) -> the enhanced recordings in input order, each what
+        :meth:`enhance` of a fresh one-utterance handle returns for it.  Every slot that was used starts from a reset."""
+        dc = self._dc(dc_mode)
+        waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
+        if any(w.ndim != 1 for w in waves):
+            raise ValueError("waves must be one-dimensional arrays")
+        hops = [max(0, (len(w) - 256) // 256) for w in waves]
+        outs = [np.zeros(len(w) + 256, np.float64) for w in waves]
+        empty = np.zeros(0, np.float32)
+        for block in plan_ragged_blocks(hops, self.utterances, self.max_frames):
+            chunks = [empty] * self.utterances
+            for slot, item, first, count, reset_before in block:
+                if reset_before:
+                    self.reset_utterance(slot)
+                chunks[slot] = waves[item][first * 256:(first + count) * 256]
+            got = self._ragged_host(self._lib.nutls_enhance_block_ragged_host, chunks, 256, dc)
+            for slot, item, first, count, _ in block:
+                outs[item][first * 256:(first + count) * 256] = got[slot]
+        return [o[256:] for o in outs]
 
     def debug_get(self, name: str, shape) -> np.ndarray:
         """Debug tensors of the handle, ``[utterances] + shape``: "phasor_block" (``shape = (n_hops, 257, 2)`` of the last analysed block)."""
