@@ -83,6 +83,50 @@ def quantize_conv_kernels(tensors: Dict[str, np.ndarray]) -> Dict[str, object]:
     return out
 
 
+EXPORT_FORMS = ("shipped", "single_scale_convs", "int8_small_dense", "float_gates")
+
+
+def _quantize(a: np.ndarray, per_channel: bool):
+    """Symmetric int8: ``scale = max|w| / 127`` (1.0 where the maximum is 0), ``q = clip(rint(w / scale), -127, 127)``; per output
+    channel (axis 0) or one scale for the tensor."""
+    a = np.asarray(a, dtype=np.float32)
+    if per_channel:
+        amax = np.abs(a).reshape(a.shape[0], -1).max(axis=1)
+        scale = np.where(amax > 0, amax / 127.0, 1.0).astype(np.float32)
+        div = scale.reshape((-1,) + (1,) * (a.ndim - 1))
+    else:
+        amax = float(np.abs(a).max()) if a.size else 0.0
+        scale = np.float32([amax / 127.0 if amax > 0 else 1.0])
+        div = scale[0]
+    return np.clip(np.rint(a / div), -127, 127).astype(np.int8), scale
+
+
+def quantize_like_export(tensors: Dict[str, np.ndarray], form: str = "shipped") -> Dict[str, object]:
+    """LSTM-variant tensors in the forms the shipped container (``weights/nutls_lstm.nutlsw``, the reference's dynamic-range export)
+    holds them.  ``form="shipped"``: conv kernels (4-D ``.w``, >= 1024 elements) and the CTFA gate matrices ``.w1`` / ``.w2`` int8 per
+    output channel; ``.wx`` / ``.wh`` and Dense ``.w`` with >= 64 outputs int8 with one scale; the 32 x 21 Dense kernels,
+    ``input_layer.w``, ``out_conv.w`` and every bias / gamma / beta / alpha float32.  The other forms are containers the fused
+    packer accepts as well (csrc/fused_host.cpp): ``"single_scale_convs"`` -- one scale per conv kernel; ``"int8_small_dense"`` --
+    the 32 x 21 Dense kernels int8 with one scale too; ``"float_gates"`` -- ``.w1`` / ``.w2`` left float32.
+    Returns name -> ndarray or ``(int8 array, scales)`` as `quantize_conv_kernels` does."""
+    if form not in EXPORT_FORMS:
+        raise ValueError("form must be one of %s" % (EXPORT_FORMS,))
+    out: Dict[str, object] = {}
+    for name, arr in tensors.items():
+        a = np.asarray(arr)
+        if name.endswith(".w") and a.ndim == 4 and a.size >= 1024:
+            out[name] = _quantize(a, per_channel=form != "single_scale_convs")
+        elif name.endswith((".w1", ".w2")) and a.ndim == 4 and form != "float_gates":
+            out[name] = _quantize(a, per_channel=True)
+        elif name.endswith((".wx", ".wh")):
+            out[name] = _quantize(a, per_channel=False)
+        elif name.endswith(".w") and a.ndim == 2 and (a.shape[0] >= 64 or form == "int8_small_dense"):
+            out[name] = _quantize(a, per_channel=False)
+        else:
+            out[name] = arr
+    return out
+
+
 def write_blob(tensors: Dict[str, object], int8_convs: bool = False) -> bytes:
     """Serialise tensors into a NUTLSW01 container: float32 arrays as they are, ``(int8 array, scales)`` tuples as int8
     payload + scales.  ``int8_convs``: quantise the conv kernels first (`quantize_conv_kernels`) -- the form the fused

@@ -1,4 +1,4 @@
-"""Oracle B -- batched float32 CPU restatement of the streaming NUNet-TLS-LSTM step
+"""Oracle B -- batched float32 (``dtype=torch.float64``: double) CPU restatement of the streaming NUNet-TLS-LSTM step
 (TEST INFRASTRUCTURE: only ``tests/``, ``__graft_entry__.smoke()`` and the
 ``cpu_baseline`` leg of ``bench.py`` may import this; the product path never does).
 
@@ -45,10 +45,16 @@ class NutlsRef:
     no trained weights exist for it, pass synthetic ones."""
 
     def __init__(self, weights: Optional[Dict[str, np.ndarray]] = None, batch: int = 1,
-                 ctfa_mode: str = "frame", variant: str = "lstm"):
+                 ctfa_mode: str = "frame", variant: str = "lstm", dtype: torch.dtype = torch.float32):
+        """``dtype=torch.float64``: the same restatement in double -- weights (the container's float32 values, widened), states,
+        attention history, scratch tensors and the input frame; what the float32 run and the kernels are measured against on weights
+        other than the trained ones."""
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
         self.variant = variant
+        self.dtype = dtype
         w = weights if weights is not None else load_weights()
-        self.w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in w.items()}
+        self.w = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dtype) for k, v in w.items()}
         self.batch = batch
         self.ctfa_mode = ctfa_mode
         self.state: Dict[str, torch.Tensor] = {}
@@ -61,11 +67,11 @@ class NutlsRef:
         self.ta_hist = {}
         for base, shp in T.state_specs(self.variant):
             if len(shp) == 1:
-                self.state[base] = torch.zeros(self.batch, shp[0])
+                self.state[base] = torch.zeros(self.batch, shp[0], dtype=self.dtype)
             elif "_ddb_" in base or base.startswith("ddb_"):
-                self.state[base.format("prev")] = torch.zeros(self.batch, *shp)      # [B, d, F, C] oldest first
+                self.state[base.format("prev")] = torch.zeros(self.batch, *shp, dtype=self.dtype)      # [B, d, F, C] oldest first
             else:
-                self.state[base.format("prev")] = torch.zeros(self.batch, shp[1], shp[2])
+                self.state[base.format("prev")] = torch.zeros(self.batch, shp[1], shp[2], dtype=self.dtype)
 
     # ---------------------------------------------------------------- blocks ------------
     def _lnp(self, y, layer):
@@ -127,7 +133,7 @@ class NutlsRef:
         (proposed.py:260-265)."""
         w = self.w[layer + ".w"]                       # [128,1,3,128] OHWI
         B, F, C = x.shape
-        full = torch.zeros(B, 2 * F + 1, w.shape[0])
+        full = torch.zeros(B, 2 * F + 1, w.shape[0], dtype=self.dtype)
         for k in range(3):
             full[:, k: k + 2 * F - 1: 2, :] += x @ w[:, 0, k, :].t()
         return full[:, : 2 * F, :] + self.w[layer + ".b"]
@@ -202,7 +208,7 @@ class NutlsRef:
         if self.ctfa_mode == "causal32":
             # the offline / training model (`ctfa`, proposed.py:125-160): ZeroPadding2D((31,0)) + AveragePooling1D(32,
             # strides=1) over the time-attention vectors of REAL frames = mean of the last 32 TA (zeros before the start)
-            hist = self.ta_hist.setdefault(prefix, torch.zeros(self.batch, 31, 64))
+            hist = self.ta_hist.setdefault(prefix, torch.zeros(self.batch, 31, 64, dtype=self.dtype))
             fa = self._mlp_gate((hist.sum(dim=1) + ta) / 32.0, prefix + "_fa")
             self.ta_hist[prefix] = torch.cat([hist[:, 1:], ta.unsqueeze(1)], dim=1)
         elif self.ctfa_mode == "frame":
@@ -242,6 +248,8 @@ class NutlsRef:
     def step(self, mag) -> torch.Tensor:
         """mag [B,256] -> enhanced magnitude [B,256]; advances the state by one frame."""
         mag = torch.as_tensor(np.asarray(mag, dtype=np.float32) if not torch.is_tensor(mag) else mag)
+        if mag.dtype != self.dtype:
+            mag = mag.to(self.dtype)
         x = self._inconv(mag.reshape(self.batch, T.N_BINS, 1), "input_layer")
         self._new: Dict[str, torch.Tensor] = {}
         enc_d, enc_down = {}, {}
@@ -272,10 +280,10 @@ class NutlsRef:
             raise ValueError("bad input names")
         for base, shp in T.state_specs():
             if len(shp) == 1:
-                self.state[base] = torch.from_numpy(np.asarray(feeds[base], np.float32).reshape(1, -1).copy())
+                self.state[base] = torch.from_numpy(np.asarray(feeds[base], np.float32).reshape(1, -1).copy()).to(self.dtype)
             else:
                 k = base.format("prev")
-                self.state[k] = torch.from_numpy(np.asarray(feeds[k], np.float32).reshape(1, shp[1], shp[2]).copy())
+                self.state[k] = torch.from_numpy(np.asarray(feeds[k], np.float32).reshape(1, shp[1], shp[2]).copy()).to(self.dtype)
         out = self.step(np.asarray(feeds["input"], np.float32).reshape(1, T.N_BINS))
         res = {"model_out": out.numpy().reshape(1, 1, T.N_BINS, 1)}
         for base, shp in T.state_specs():
