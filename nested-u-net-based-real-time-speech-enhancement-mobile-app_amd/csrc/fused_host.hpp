@@ -1,5 +1,6 @@
 // What the host knows about a static plan of the fused frame-step kernel (fused_plan_*.inc): one immutable descriptor per plan.
-// Host only: engine.cpp and fused_host.cpp include it, no kernel translation unit does (an edit here re-compiles no kernel).
+// Host only: fused_host.cpp and, through engine.hpp, the five files of the host engine (engine.cpp, api_stream.cpp, api_block.cpp, api_state.cpp,
+// api_profile.cpp) include it, no kernel translation unit does (an edit here re-compiles no kernel).
 #pragma once
 
 #include "nutls_internal.hpp"

@@ -47,6 +47,25 @@ def test_bad_arguments_are_reported(lib):
     buf = (ctypes.c_float * 4)()
     lib.nutls_host_free(ctypes.addressof(buf))
     assert lib.nutls_profile_production(None, None, 0, 1, 1) == -1
+    # One error slot for the whole library: the C ABI lives in five host files (engine.cpp, api_stream.cpp, api_block.cpp, api_state.cpp,
+    # api_profile.cpp) and nutls_last_error() is defined in the first -- a failure raised in any of them must be what it returns.  In front
+    # of every call another message (no "null" in it) is left in the slot, so a stale text cannot pass for the call's own.
+    null_handle = {
+        "engine.cpp": (lambda: lib.nutls_batch(None), b"null handle"),
+        "api_stream.cpp": (lambda: lib.nutls_step_host(None, None, None), b"nutls_step_host: null pointer"),
+        "api_block.cpp": (lambda: lib.nutls_enhance_block_host(None, None, None, 1, 0), b"nutls_enhance_block_host: null pointer"),
+        "api_state.cpp": (lambda: lib.nutls_state_get(None, b"x", None, 0), b"nutls_state_get: null pointer"),
+        "api_profile.cpp": (lambda: lib.nutls_profile_step(None, None, 0), b"nutls_profile_step: null pointer"),
+    }
+    for where, (call, text) in null_handle.items():
+        assert lib.nutls_create(b"x", 1, 7, 1, 0, ctypes.byref(h)) == runner.NUTLS_ERR_ARG
+        assert lib.nutls_last_error() == b"nutls_create: unknown variant"
+        assert call() == runner.NUTLS_ERR_ARG, where
+        err = lib.nutls_last_error()
+        assert err and b"null" in err and err == text, (where, err)
+    for call in (lambda: lib.nutls_reset(None, 0), lambda: lib.nutls_debug_knob(None, None, 0), lambda: lib.nutls_process_block_host(None, None, None, 1)):
+        assert lib.nutls_create(b"x", 1, 7, 1, 0, ctypes.byref(h)) == runner.NUTLS_ERR_ARG
+        assert call() == runner.NUTLS_ERR_ARG and b"null" in lib.nutls_last_error()
 
 
 def test_no_cpu_fallback(lib):
