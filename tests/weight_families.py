@@ -1,10 +1,16 @@
 """Synthetic weight families, inputs and float64 reference values for the LSTM-variant kernels (a plain helper module: the CPU tests
-of tests/test_weight_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py share it, and its caches).
+of tests/test_weight_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py share it, and its caches) and, in its second
+half (``variant="baseline"``), for the dilated-dense baseline's (tests/test_baseline_families.py, tests/test_gpu_baseline_families.py).
 
 Every family starts from ``synthetic_weights("lstm", SEED, bias_std=0.1, affine_jitter=0.1)`` and is stored as the export stores the
 trained network (``weights.quantize_like_export``); the oracle is fed ``parse_blob`` of the very container the engine is given, so
 quantisation is not part of any difference measured here.  The reference is oracle B in double (``NutlsRef(dtype=torch.float64)``);
-the float32 oracle's distance from it is what decides whether a family is fit to test with (the conditioning cap)."""
+the float32 oracle's distance from it is what decides whether a family is fit to test with (the conditioning cap).
+
+The baseline half: every family starts from ``synthetic_weights("baseline", SEED, bias_std=0.1, affine_jitter=0.1)``, is stored with
+``write_blob(..., int8_convs=True)`` (the form the fused kernel takes) and runs BASE_FRAMES = 37 frames: block 6 of every dilated-dense
+block taps the frame 32 steps back, so its history is live for the last 5 frames only, and at 37 every history ring of depth >= 2 sits at
+a non-zero phase (37 & (d - 1) = 1, 1, 5, 5, 5 for d = 2, 4, 8, 16, 32)."""
 import functools
 
 import numpy as np
@@ -35,14 +41,29 @@ ALPHAS = np.float32([-0.5, 0.0, 1.0, 1.7])
 # draw gives 6.1e-7 on the traced tensors and 6.1e-7 x scale on the states.
 SCALES_SEED = 41
 
-BASE_FAMILIES = ("plain", "satbias", "const", "dead", "scales", "alpha")
+# LayerNorm variance about equal to its epsilon (1e-8): the kernel times 3e-4, the bias zero so that nothing cancels.  With a variance of
+# exactly 0 (`const`) the output is beta whatever a non-zero eps is, and on plain weights eps is 1e-8 next to a variance of order 1; here
+# the output depends on eps to first order, at every site that sets it in its own place in the code.
+TINYVAR_CONVS = ("input_layer", "msfe5_en_conv2", "msfe4_de_spconv1", "msfe6_de_in", "msfe6_de_spconv6")
+TINYVAR_FACTOR = np.float32(3e-4)
+
+BASE_FAMILIES = ("plain", "satbias", "const", "dead", "scales", "alpha", "tinyvar")
 FORM_FAMILIES = tuple("forms_" + f for f in EXPORT_FORMS if f != "shipped")
 FAMILIES = BASE_FAMILIES + FORM_FAMILIES
 
 
-def state_names():
-    """The 130 state tensors under the names ``state_get`` and ``NutlsRef.state`` use."""
-    return [base if len(shp) == 1 else base.format("prev") for base, shp in T.state_specs()]
+# ---- the baseline half's constants -----------------------------------------------------------------------------------------------------
+BASE_FRAMES = 37
+BASELINE_FAMILIES = ("plain", "const", "tinyvar", "alpha", "dead", "scales")
+# one block each of an F = 4, an F = 2 and an F = 1 stage (G = 16) and of the central block (F = 4, G = 32)
+CONST_BLOCKS = ("msfe6_en_ddb_3", "msfe4_de2_ddb_2", "msfe4_en3_ddb_1", "ddb_6")
+TINYVAR_BLOCKS = ("msfe6_en_ddb_2", "ddb_4", "msfe4_en3_ddb_6", "msfe4_de2_ddb_1", "msfe6_de_ddb_5")
+DEAD_BLOCKS = ("ddb_3", "msfe4_en2_ddb_5", "msfe3_de_ddb_2")          # (F, G) = (4, 32), (2, 16), (1, 16)
+
+
+def state_names(variant="lstm"):
+    """The 130 (LSTM variant) or 208 (baseline) state tensors under the names ``state_get`` and ``NutlsRef.state`` use."""
+    return [base if len(shp) == 1 else base.format("prev") for base, shp in T.state_specs(variant)]
 
 
 def traced_names():
@@ -55,8 +76,57 @@ def traced_shape(name):
     return (T.STAGE_BY_PREFIX[prefix].f0, 64 if kind == "y" else 128)
 
 
-def family_tensors(family):
+def _scale_rows(a, rng):
+    """2^k, k in [-6, 2], per output channel (axis 0): exact, nine octaves of per-channel scales"""
+    e = rng.integers(-6, 3, size=a.shape[0])
+    return (a * np.exp2(e).reshape((-1,) + (1,) * (a.ndim - 1))).astype(np.float32)
+
+
+def _baseline_tensors(family):
+    w = synthetic_weights("baseline", SEED, bias_std=0.1, affine_jitter=0.1)
+    if family == "plain":
+        return w
+    if family == "const":
+        # z = b1 = 0.5 in every channel: the block's LayerNorm sees a variance of exactly 0 and the block's output is PReLU(beta)
+        for blk in CONST_BLOCKS:
+            w[blk + ".w1"] = np.zeros_like(w[blk + ".w1"])
+            w[blk + ".b1"] = np.full_like(w[blk + ".b1"], 0.5)
+        for layer in CONST_LAYERS:
+            w[layer + ".w"] = np.zeros_like(w[layer + ".w"])
+            w[layer + ".b"] = np.full_like(w[layer + ".b"], 0.5)
+    elif family == "tinyvar":
+        for blk in TINYVAR_BLOCKS:
+            w[blk + ".w1"] = (w[blk + ".w1"] * TINYVAR_FACTOR).astype(np.float32)
+            w[blk + ".b1"] = np.zeros_like(w[blk + ".b1"])
+        for layer in TINYVAR_CONVS:
+            w[layer + ".w"] = (w[layer + ".w"] * TINYVAR_FACTOR).astype(np.float32)
+            w[layer + ".b"] = np.zeros_like(w[layer + ".b"])
+    elif family == "alpha":
+        # sorted order puts the eight slopes of one block (_1 .. _6, _in, _out) next to each other: they differ inside every block
+        for n, k in enumerate(sorted(k for k in w if k.endswith(".alpha"))):
+            w[k] = np.full_like(w[k], ALPHAS[n % 4])
+    elif family == "dead":
+        for blk in DEAD_BLOCKS:
+            w[blk + ".w1"][::3] = 0.0          # the 1x1 conv's output channel is its bias alone
+            w[blk + ".wg"][1::3] = 0.0         # the grouped conv's output channel is its bias alone
+        for layer in DEAD_LAYERS:
+            w[layer + ".w"][::3] = 0.0          # all-zero output channels: quantiser scale 1.0
+    elif family == "scales":
+        rng = np.random.default_rng(SCALES_SEED)
+        for k in w:
+            if k.endswith(".w") and w[k].ndim == 4 and w[k].size >= 1024:
+                w[k] = _scale_rows(w[k], rng)
+            elif k.endswith(".w1") and w[k].ndim == 2:          # the rows of every block's 1x1 kernel
+                w[k] = _scale_rows(w[k], rng)
+    else:
+        raise ValueError("unknown baseline family %s" % family)
+    return w
+
+
+def family_tensors(family, variant="lstm"):
     """Float32 tensors of a family, before quantisation."""
+    if variant == "baseline":
+        return _baseline_tensors(family)
     w = synthetic_weights("lstm", SEED, bias_std=0.1, affine_jitter=0.1)
     if family == "plain" or family.startswith("forms_"):
         return w
@@ -81,15 +151,24 @@ def family_tensors(family):
     elif family == "alpha":
         for n, k in enumerate(sorted(k for k in w if k.endswith(".alpha"))):
             w[k] = np.full_like(w[k], ALPHAS[n % 4])
+    elif family == "tinyvar":
+        for layer in TINYVAR_CONVS:
+            w[layer + ".w"] = (w[layer + ".w"] * TINYVAR_FACTOR).astype(np.float32)
+            w[layer + ".b"] = np.zeros_like(w[layer + ".b"])
     else:
         raise ValueError("unknown family %s" % family)
     return w
 
 
 @functools.lru_cache(maxsize=None)
-def container(family, form=None):
+def container(family, form=None, variant="lstm"):
     """The family's container.  ``form``: an export form of ``quantize_like_export`` ("shipped" unless the family is one of the
-    ``forms_*``), or "float" (no quantisation at all: per-layer kernels only)."""
+    ``forms_*``), or "float" (no quantisation at all: per-layer kernels only).  Baseline: ``write_blob(..., int8_convs=True)`` (form
+    None) or "float"."""
+    if variant == "baseline":
+        if form not in (None, "float"):
+            raise ValueError("the baseline containers are the int8-conv one (form None) and \"float\"")
+        return write_blob(family_tensors(family, variant), int8_convs=form is None)
     if form is None:
         form = family[len("forms_"):] if family.startswith("forms_") else "shipped"
     w = family_tensors(family)
@@ -109,13 +188,34 @@ def base_streams():
     return x
 
 
-def inputs(batch):
-    """[FRAMES, batch, 256]: the base streams, repeated (stream b is base stream b % 4)."""
+BASE_TAIL = 8          # frames past BASE_FRAMES that the baseline streams' generators go on for (the state-transplant test)
+
+
+@functools.lru_cache(maxsize=None)
+def baseline_streams():
+    """[BASE_FRAMES + BASE_TAIL, 4, 256] float32: the recipe of `base_streams` for the baseline half, with seeds of its own (one
+    generator per noise stream, so that the first BASE_FRAMES frames do not depend on how far the generators are run)."""
+    n = BASE_FRAMES + BASE_TAIL
+    x = np.zeros((n, 4, 256), np.float32)
+    x[:, 0] = 0.25 * np.abs(np.random.default_rng([SEED + 5, 0]).standard_normal((n, 256)))
+    x[2:, 1, 40] = 50.0
+    x[:, 2] = 0.25 * np.abs(np.random.default_rng([SEED + 5, 2]).standard_normal((n, 256)))
+    x[:, 3] = 1e-20
+    x.setflags(write=False)
+    return x
+
+
+def inputs(batch, variant="lstm", tail=False):
+    """[FRAMES, batch, 256]: the base streams, repeated (stream b is base stream b % 4).  Baseline: [BASE_FRAMES, batch, 256], or with
+    ``tail`` the BASE_TAIL frames that follow."""
+    if variant == "baseline":
+        x = baseline_streams()[BASE_FRAMES:] if tail else baseline_streams()[:BASE_FRAMES]
+        return np.ascontiguousarray(x[:, np.arange(batch) % 4])
     return np.ascontiguousarray(base_streams()[:, np.arange(batch) % 4])
 
 
 BLOCK_FRAMES = 27
-BLOCK_FAMILIES = ("plain", "satbias", "const", "dead")          # the families the block mode runs (2 utterances, BLOCK_FRAMES frames)
+BLOCK_FAMILIES = ("plain", "satbias", "const", "dead", "tinyvar")          # the families the block mode runs (2 utterances, BLOCK_FRAMES frames)
 
 
 @functools.lru_cache(maxsize=None)
@@ -141,23 +241,36 @@ class Run:
             a.setflags(write=False)
 
 
-def _oracle(blob, x, dtype, trace):
-    """x [frames, B, 256] through oracle B in ``dtype``"""
-    ref = NutlsRef(parse_blob(blob), batch=x.shape[1], dtype=dtype)
+def _oracle(blob, x, dtype, trace, variant="lstm", state=None):
+    """x [frames, B, 256] through oracle B in ``dtype``; ``state``: the state tensors to start from (zeros otherwise)"""
+    ref = NutlsRef(parse_blob(blob), batch=x.shape[1], dtype=dtype, variant=variant)
+    if state is not None:
+        for n in state_names(variant):
+            assert ref.state[n].shape == state[n].shape, n
+            ref.state[n] = torch.from_numpy(np.array(state[n])).to(dtype)
     outs, tr = [], {n: [] for n in traced_names()} if trace else {}
     for f in range(x.shape[0]):
         ref.trace = {} if trace else None
         outs.append(ref.step(x[f]).numpy().astype(np.float64))
         for n in tr:
             tr[n].append(ref.trace[n].numpy().astype(np.float64))
-    state = {n: ref.state[n].numpy().astype(np.float64) for n in state_names()}
+    state = {n: ref.state[n].numpy().astype(np.float64) for n in state_names(variant)}
     return Run(np.stack(outs), {n: np.stack(v) for n, v in tr.items()}, state)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(family, dtype=torch.float64, form=None):
+def reference(family, dtype=torch.float64, form=None, variant="lstm"):
     """The four base streams through the oracle on the family's container (computed once per process, never modified)."""
-    return _oracle(container(family, form), inputs(4), dtype, trace=True)
+    return _oracle(container(family, form, variant), inputs(4, variant), dtype, trace=True, variant=variant)
+
+
+@functools.lru_cache(maxsize=None)
+def baseline_continuation(family):
+    """The float64 baseline reference carried on from its states after frame BASE_FRAMES through the BASE_TAIL frames that follow
+    (the state tensors are all of the oracle's state, so this is the run of BASE_FRAMES + BASE_TAIL frames)."""
+    start = reference(family, variant="baseline")
+    return _oracle(container(family, variant="baseline"), inputs(4, "baseline", tail=True), torch.float64, trace=False, variant="baseline",
+                   state=start.state)
 
 
 @functools.lru_cache(maxsize=None)
@@ -182,10 +295,35 @@ def rel_rms(got, want):
     return rms(got, want) / max(1e-12, float(np.sqrt(np.mean(want ** 2))))
 
 
+def ddb_state(name):
+    """``X_ddb_prev_in`` / ``X_ddb_prevK`` / ``X_ddb_prev_out`` (central: ``ddb_...``) -> (the plan's op name ``X_ddb`` / ``ddb``, "in" /
+    K / "out"); None for any other state."""
+    for prefix, _, _ in T.bottlenecks():
+        tag = (prefix + "_ddb") if prefix else "ddb"
+        if name.startswith(tag + "_prev"):
+            part = name[len(tag) + 5:]
+            if part in ("_in", "_out"):
+                return tag, part[1:]
+            if part.isdigit() and 1 <= int(part) <= T.DDB_BLOCKS:
+                return tag, int(part)
+    return None
+
+
+def state_label(name, stream):
+    """What a ledger calls a state tensor of a stream; a block's history ring says which block's output its newest frame starts with."""
+    d = ddb_state(name)
+    if d is not None and isinstance(d[1], int):
+        return "state %s (block %d output, newest frame), stream %d" % (name, d[1] - 1, stream)
+    return "state %s, stream %d" % (name, stream)
+
+
 def state_consumer(name):
-    """The layer of the fused plan that a state tensor belongs to: the conv whose previous-frame input it is, or the stage's LSTM."""
+    """The layer of the fused plan that a state tensor belongs to: the conv whose previous-frame input it is, the stage's LSTM, or
+    (baseline) the dilated-dense block op."""
     if name in ("state_h", "state_c"):
         return "lstm"
+    if ddb_state(name) is not None:
+        return ddb_state(name)[0]
     for st in T.STAGES:
         if name in (st.prefix + "_h", st.prefix + "_c"):
             return st.prefix + "_lstm"
