@@ -349,6 +349,18 @@ int nutls_launches_per_step(nutls_handle* h);
  * elements written)  -- the "layer-fused" traffic model of SURVEY.md section 8(d). */
 int nutls_launch_info(nutls_handle* h, int index, const char** layer, const char** family,
                       double* flops, double* bytes);
+/* The conv launches of that plan: kind (0 .. 9: el_c32, el_c64, el_c128, dl_n64, dl_n128, in_c64, in_c128, down, up_even, up_odd) and output
+ * positions per stream; kind = -1, f_out = 0 for a launch that is no conv.  The block plan of an offline handle has the same entries. */
+int nutls_launch_conv_shape(nutls_handle* h, int index, int* kind, int* f_out);
+/* Which instantiation of the per-layer conv kernels a launch of `batch` streams (block mode: utterances x frames of the launch) x `f_out`
+ * positions of that kind runs -- the library's one rule, the function its launches dispatch on.  Host only: no handle, no device.
+ * bf16 != 0: conv_bf16x3_kernel (block mode on an int8 container), else conv_mfma_kernel.  ksplit / tile_min: the developer knobs
+ * NUTLS_OFFLINE_KSPLIT (default 1) and NUTLS_CONV_TILE_MIN (positions per launch from which the 128-position tiles run; < 0: the
+ * defaults, 32768 bf16 / 65536 fp32), which a handle reads from the environment when it is created.
+ * Out (each may be null): template arguments NW and ALL ((4, 1) = the K split; fp32: all = 0), positions per workgroup (32 / 128),
+ * workgroups (the last one partly filled where batch * f_out is no multiple of the tile), bytes of dynamic LDS. */
+int nutls_conv_dispatch(int kind, int batch, int f_out, int bf16, int ksplit, long long tile_min, int* nw, int* all, int* tile,
+                        long long* grid, long long* lds_bytes);
 
 /* Run ONE step with plain launches on the library's own stream, bracketing every launch with
  * HIP events recorded on that stream; writes the milliseconds of each launch to ms[0..n).

@@ -149,7 +149,7 @@ static int launch_block_range(Engine* e, size_t first, size_t last, int t0, int 
         L.conv.B = U * n;
         L.conv.sm = sm;
         L.conv.use_bf16 = e->off_bf16 && L.conv.wbf != nullptr;
-        err = launch_conv(L.ck, L.conv, s);
+        err = launch_conv(L.ck, L.conv, s, e->conv_knobs);
         break;
       case Launch::LSTM:
         shc(L.lstm.x); sh(L.lstm.dst); shc(L.lstm.h_in); shc(L.lstm.c_in); sh(L.lstm.h_out); sh(L.lstm.c_out);

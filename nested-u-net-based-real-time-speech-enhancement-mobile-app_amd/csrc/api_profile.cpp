@@ -36,13 +36,13 @@ int nutls_debug_trace(nutls_handle* h, int enable) {
   return NUTLS_OK;
 }
 
-static const char* family_name(const Launch& L, int B) {
+static const char* family_name(const Launch& L, int B, const ConvKnobs& kn) {
   static const char* conv_names[CONV_KIND_COUNT] = {"conv_el_c32", "conv_el_c64", "conv_el_c128", "conv_dl_n64", "conv_dl_n128",
                                                     "conv_in_c64", "conv_in_c128", "conv_down", "conv_up_even", "conv_up_odd"};
   static std::string tmp[2 * CONV_KIND_COUNT];
   switch (L.kind) {
     case Launch::CONV: {
-      const int nw = conv_pick_nw(L.ck, B, L.conv.F_out);
+      const int nw = conv_choose(L.ck, B, L.conv.F_out, false, kn).nw;
       std::string& t = tmp[2 * L.ck + (nw == 4)];
       t = std::string(conv_names[L.ck]) + (nw == 4 ? "/w4" : "/w1");
       return t.c_str();
@@ -96,9 +96,33 @@ int nutls_launch_info(nutls_handle* h, int index, const char** layer, const char
     }
   }
   if (layer) *layer = L.name.c_str();
-  if (family) *family = family_name(L, e->B);
+  if (family) *family = family_name(L, e->B, e->conv_knobs);
   if (flops) *flops = fl;
   if (bytes) *bytes = by;
+  return NUTLS_OK;
+}
+
+int nutls_launch_conv_shape(nutls_handle* h, int index, int* kind, int* f_out) {
+  if (!h || !kind || !f_out || index < 0 || index >= static_cast<int>(h->eng.plan[0].size())) return fail(NUTLS_ERR_ARG, "nutls_launch_conv_shape: null pointer or bad index");
+  const Launch& L = h->eng.plan[0][index];
+  const bool conv = L.kind == Launch::CONV;
+  *kind = conv ? static_cast<int>(L.ck) : -1;
+  *f_out = conv ? L.conv.F_out : 0;
+  return NUTLS_OK;
+}
+
+int nutls_conv_dispatch(int kind, int batch, int f_out, int bf16, int ksplit, long long tile_min, int* nw, int* all, int* tile, long long* grid, long long* lds_bytes) {
+  if (kind < 0 || kind >= CONV_KIND_COUNT) return fail(NUTLS_ERR_ARG, "nutls_conv_dispatch: unknown conv kind");
+  if (batch < 1 || f_out < 1 || (f_out & (f_out - 1))) return fail(NUTLS_ERR_ARG, "nutls_conv_dispatch: batch must be >= 1 and f_out a power of two");
+  ConvKnobs kn;
+  kn.ksplit = ksplit != 0;
+  kn.tile_min = tile_min;
+  const ConvChoice c = conv_choose(static_cast<ConvKind>(kind), batch, f_out, bf16 != 0, kn);
+  if (nw) *nw = c.nw;
+  if (all) *all = c.all;
+  if (tile) *tile = c.tile;
+  if (grid) *grid = c.grid;
+  if (lds_bytes) *lds_bytes = static_cast<long long>(c.lds);
   return NUTLS_OK;
 }
 
@@ -116,7 +140,7 @@ int nutls_profile_step(nutls_handle* h, float* ms, int n) {
   if (int rc = begin_per_layer_step(e, e->stream)) return rc;
   HIP_TRY(hipEventRecord(ev[0], e->stream));
   for (size_t i = 0; i < plan.size(); ++i) {
-    HIP_TRY(run_launch(plan[i], e->stream));
+    HIP_TRY(run_launch(plan[i], e->stream, e->conv_knobs));
     HIP_TRY(hipEventRecord(ev[i + 1], e->stream));
   }
   if (e->variant == NUTLS_VARIANT_BASELINE) HIP_TRY(launch_incr_step(e->d_step, e->stream));

@@ -617,9 +617,9 @@ static void build_plan(Engine* e, int par) {
   plan->push_back(L);
 }
 
-hipError_t run_launch(const Launch& L, hipStream_t s) {
+hipError_t run_launch(const Launch& L, hipStream_t s, const ConvKnobs& kn) {
   switch (L.kind) {
-    case Launch::CONV: return launch_conv(L.ck, L.conv, s);
+    case Launch::CONV: return launch_conv(L.ck, L.conv, s, kn);
     case Launch::LSTM: return launch_lstm(L.lstm, s);
     case Launch::CTFA: return launch_ctfa(L.ctfa, s);
     case Launch::INLAYER: return launch_input_layer(L.inl, s);
@@ -631,7 +631,7 @@ hipError_t run_launch(const Launch& L, hipStream_t s) {
 
 int run_plan(Engine* e, int par, hipStream_t s) {
   for (const Launch& L : e->plan[par]) {
-    hipError_t err = run_launch(L, s);
+    hipError_t err = run_launch(L, s, e->conv_knobs);
     if (err != hipSuccess) return fail(NUTLS_ERR_HIP, "launch " + L.name + ": " + hipGetErrorString(err));
   }
   if (e->variant == NUTLS_VARIANT_BASELINE) HIP_TRY(launch_incr_step(e->d_step, s));   // ring position of the dilated-dense history
@@ -1033,6 +1033,9 @@ static int create_body(const void* weights, size_t n_bytes, int variant, int bat
   e->variant = variant;
   e->fz_plan = fused_plan(variant, 1);      // (until fused_setup chooses: what the handle-independent questions about "the plan" mean)
   e->off_bf16 = offline_frames > 0 && getenv("NUTLS_OFFLINE_FP32") == nullptr;      // (developer knob: block mode on the fp32-MFMA kernels)
+  // (developer knobs of conv_choose: the small bf16 launches on the 1-wave kernels; the positions per launch from which the 128-position tiles run)
+  if (const char* ev = getenv("NUTLS_OFFLINE_KSPLIT")) e->conv_knobs.ksplit = atoi(ev) != 0;
+  if (const char* ev = getenv("NUTLS_CONV_TILE_MIN")) e->conv_knobs.tile_min = atoll(ev);
   HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   int rc;
   if ((rc = prep_weights(e, wm))) return rc;

@@ -168,6 +168,8 @@ struct Engine {
                          // its carried state, then its frames
   std::vector<Launch> plan_off;   // plan[0] with 'previous frame' = one arena slot earlier
   bool off_bf16 = false;          // block mode: convs on the bf16 matrix pipe where the container holds int8 kernels (NUTLS_OFFLINE_FP32=1: the fp32-MFMA kernels)
+  ConvKnobs conv_knobs;           // developer knobs of the per-layer convs' choice of instantiation (NUTLS_OFFLINE_KSPLIT, NUTLS_CONV_TILE_MIN), read when the
+                                  // handle is created like NUTLS_OFFLINE_FP32: every per-layer conv launch of this handle, block or streaming, is chosen under them
   float* zx = nullptr;   // [offline + kScanReadAhead][84] LSTM input products of a block
   int ctfa_causal = 0;   // offline handles: 1 = true 32-frame causal average in the CTFA frequency branch (proposed.py:143-147)
   float* ta_hist = nullptr;   // [12 stages][31 + offline][64] time-attention history (causal mode)
@@ -213,7 +215,7 @@ int dev_alloc_once(Engine* e, size_t n, T** out, bool zero) {
   return NUTLS_OK;
 }
 
-hipError_t run_launch(const Launch& L, hipStream_t s);
+hipError_t run_launch(const Launch& L, hipStream_t s, const ConvKnobs& kn);
 int run_plan(Engine* e, int par, hipStream_t s);
 int states_materialize(Engine* e, hipStream_t s);
 int run_fused(Engine* e, int par, hipStream_t s, bool prof, const float* mag_in = nullptr, float* mag_out = nullptr,

@@ -483,7 +483,7 @@ ConvShape conv_shape(ConvKind k) {
   }
 }
 
-size_t conv_lds_bytes(ConvKind k, int f_out, int nw) {
+static size_t conv_lds_bytes(ConvKind k, int f_out, int nw) {
   const ConvShape s = conv_shape(k);
   const int cc = s.cin < 64 ? s.cin : 64;
   const int tp = 32 * nw;
@@ -505,10 +505,47 @@ static size_t conv_lds_bytes_bf16(ConvKind k, int f_out, int nw) {
   return static_cast<size_t>(nseg) * rs * pitch_b;
 }
 
-int conv_pick_nw(ConvKind, int B, int f_out) {
-  // 4-wave workgroups (128 positions) once there are enough positions to give every CU several
-  // workgroups; single-wave workgroups otherwise so small layers spread over more CUs.
-  return (static_cast<long long>(B) * f_out >= 128LL * 512) ? 4 : 1;
+// What makes an instantiation of conv_bf16x3_kernel exist for a kind (launch_conv_t guards its dispatch with the same two conditions, as
+// `if constexpr`, so that nothing else is compiled): nph = phases, wph = weight fragments of a phase, ksteps = K steps of all phases.
+struct ConvStatic { int nph, wph, ksteps; };
+constexpr ConvStatic conv_static(int cin, int nt, int tt, int kf) {
+  const int cc = cin < 64 ? cin : 64;
+  return {tt * (cin / cc), kf * (cc / 16) * nt, tt * (cin / cc) * kf * (cc / 16)};
+}
+constexpr bool conv_has_ksplit(ConvStatic c) { return c.ksteps % 4 == 0 && c.nph * c.wph <= 192; }      // <.., 4, true>: the K steps deal evenly to four waves and a wave's quarter of the weights fits its registers
+constexpr bool conv_has_all1(ConvStatic c) { return c.nph > 1 && c.nph * c.wph <= 48; }                  // <.., 1, true>: all phases side by side, all weights in the registers of one wave
+
+// What one workgroup may ask for: the LDS of a gfx950 CU.  The 128-position image of a tile of 128 one-position segments outgrows it for the
+// strided 64-channel-chunk kinds on the bf16 pipe (el_c64, el_c128, down at f_out = 1: 128 segments x 2 row pairs x 784 B = 200 704 B) --
+// such a launch stays on the 32-position tiles whatever its size (it could not start: hipFuncSetAttribute refuses the size).
+constexpr size_t kLdsMax = 160 * 1024;
+
+ConvChoice conv_choose(ConvKind k, int B, int f_out, bool bf16, const ConvKnobs& kn) {
+  const long long total = static_cast<long long>(B) * f_out;
+  auto tiles = [&](int tile) { return static_cast<unsigned>((total + tile - 1) / tile); };
+  if (!bf16) {
+    // 4-wave workgroups (128 positions) once there are enough positions to give every CU several
+    // workgroups; single-wave workgroups otherwise so small layers spread over more CUs.
+    const int nw = total >= (kn.tile_min >= 0 ? kn.tile_min : 128LL * 512) && conv_lds_bytes(k, f_out, 4) <= kLdsMax ? 4 : 1;
+    return {nw, 0, 32 * nw, 64 * nw, tiles(32 * nw), conv_lds_bytes(k, f_out, nw)};
+  }
+  // 128-position tiles from 32 k positions per launch on, below that the K-split kernel on 32-position tiles (measured at
+  // 16 k .. 1 M positions: 293 k frames/s at 16-32 k, 288 k at 64 k and above; one 1024-frame utterance, three chunks)
+  const int nw = total >= (kn.tile_min >= 0 ? kn.tile_min : 64LL * 512) && conv_lds_bytes_bf16(k, f_out, 4) <= kLdsMax ? 4 : 1;
+  const size_t ldsb = conv_lds_bytes_bf16(k, f_out, nw);
+  if (nw == 4) return {4, 0, 128, 256, tiles(128), ldsb};
+  // 1-wave workgroups (the layers with few positions): all phases at once where LDS and the registers allow it
+  const ConvShape sh = conv_shape(k);
+  const ConvStatic st = conv_static(sh.cin, sh.nt, sh.tt, sh.kf);
+  const size_t phase_b = (ldsb + 255) & ~static_cast<size_t>(255);
+  // four waves on the K steps of one 32-position tile where the K steps deal evenly and a wave's quarter of the weights fits
+  // its registers; the exchange buffer (3 waves x NT x 4 KB) re-uses the image
+  if (conv_has_ksplit(st)) {
+    const size_t need = std::max<size_t>(st.nph * phase_b, static_cast<size_t>(3) * sh.nt * 4096);
+    if (kn.ksplit && need <= 128 * 1024) return {4, 1, 32, 256, tiles(32), need};
+  }
+  if (conv_has_all1(st) && st.nph * phase_b <= 64 * 1024) return {1, 1, 32, 64, tiles(32), st.nph * phase_b};
+  return {1, 0, 32, 64, tiles(32), ldsb};
 }
 
 constexpr int kMaxDevices = 64;
@@ -533,52 +570,42 @@ static hipError_t launch_conv_variant(size_t lds, unsigned grid, unsigned thread
 }
 
 template <int CIN, int NT, int STRIDE, int TT, int KF, int PADL, int EPI_LN, int G>
-static hipError_t launch_conv_t(ConvKind k, const ConvParams& p, hipStream_t s) {
-  if (p.use_bf16 && p.wbf && p.wscale) {      // block mode on an int8 container: the bf16-pipe kernel
-    // 128-position tiles from 32 k positions per launch on, below that the K-split kernel on 32-position tiles (measured at
-    // 16 k .. 1 M positions: 293 k frames/s at 16-32 k, 288 k at 64 k and above; one 1024-frame utterance, three chunks)
-    const long long totalb = static_cast<long long>(p.B) * p.F_out;
-    const int nw = totalb >= 64LL * 512 ? 4 : 1;
-    const size_t ldsb = conv_lds_bytes_bf16(k, p.F_out, nw);
-    if (nw == 4)
-      return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4, false>>(ldsb, static_cast<unsigned>((totalb + 127) / 128), 256, p, s);
-    // 1-wave workgroups (the layers with few positions): all phases at once where LDS and the registers allow it
-    constexpr int cc = CIN < 64 ? CIN : 64, nph = TT * (CIN / cc), wph = KF * (cc / 16) * NT;
-    const size_t phase_b = (ldsb + 255) & ~static_cast<size_t>(255);
-    // four waves on the K steps of one 32-position tile where the K steps deal evenly and a wave's quarter of the weights fits
-    // its registers; the exchange buffer (3 waves x NT x 4 KB) re-uses the image
-    static const bool ksplit = [] { const char* v = getenv("NUTLS_OFFLINE_KSPLIT"); return !v || atoi(v) != 0; }();
-    if constexpr ((nph * KF * (cc / 16)) % 4 == 0 && nph * wph <= 192) {
-      const size_t need = std::max<size_t>(nph * phase_b, 3 * NT * 4096);
-      if (ksplit && need <= 128 * 1024)
-        return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4, true>>(need, static_cast<unsigned>((totalb + 31) / 32), 256, p, s);
+static hipError_t launch_conv_t(ConvKind k, const ConvParams& p, hipStream_t s, const ConvKnobs& kn) {
+  const bool bf16 = p.use_bf16 && p.wbf && p.wscale;      // block mode on an int8 container: the bf16-pipe kernel
+  const ConvChoice c = conv_choose(k, p.B, p.F_out, bf16, kn);
+  if (bf16) {
+    constexpr ConvStatic st = conv_static(CIN, NT, TT, KF);
+    if (c.nw == 4 && !c.all)
+      return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4, false>>(c.lds, c.grid, c.threads, p, s);
+    if constexpr (conv_has_ksplit(st)) {
+      if (c.nw == 4 && c.all)
+        return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4, true>>(c.lds, c.grid, c.threads, p, s);
     }
-    if constexpr (nph > 1 && nph * wph <= 48) {
-      if (nph * phase_b <= 64 * 1024)
-        return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1, true>>(nph * phase_b, static_cast<unsigned>((totalb + 31) / 32), 64, p, s);
+    if constexpr (conv_has_all1(st)) {
+      if (c.nw == 1 && c.all)
+        return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1, true>>(c.lds, c.grid, c.threads, p, s);
     }
-    return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1, false>>(ldsb, static_cast<unsigned>((totalb + 31) / 32), 64, p, s);
+    if (c.nw == 1 && !c.all)
+      return launch_conv_variant<conv_bf16x3_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1, false>>(c.lds, c.grid, c.threads, p, s);
+    return hipErrorInvalidValue;      // (conv_choose named an instantiation this kind does not have: the two conditions above are its own)
   }
-  const int nw = conv_pick_nw(k, p.B, p.F_out);
-  const size_t lds = conv_lds_bytes(k, p.F_out, nw);
-  const long long total = static_cast<long long>(p.B) * p.F_out;
-  if (nw == 4)
-    return launch_conv_variant<conv_mfma_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4>>(lds, static_cast<unsigned>((total + 127) / 128), 256, p, s);
-  return launch_conv_variant<conv_mfma_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1>>(lds, static_cast<unsigned>((total + 31) / 32), 64, p, s);
+  if (c.nw == 4)
+    return launch_conv_variant<conv_mfma_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 4>>(c.lds, c.grid, c.threads, p, s);
+  return launch_conv_variant<conv_mfma_kernel<CIN, NT, STRIDE, TT, KF, PADL, EPI_LN, G, 1>>(c.lds, c.grid, c.threads, p, s);
 }
 
-hipError_t launch_conv(ConvKind k, const ConvParams& p, hipStream_t s) {
+hipError_t launch_conv(ConvKind k, const ConvParams& p, hipStream_t s, const ConvKnobs& kn) {
   switch (k) {
-    case CONV_EL_C32:   return launch_conv_t<32,  1, 2, 2, 3, 1, 1, 1>(k, p, s);
-    case CONV_EL_C64:   return launch_conv_t<64,  1, 2, 2, 3, 1, 1, 1>(k, p, s);
-    case CONV_EL_C128:  return launch_conv_t<128, 1, 2, 2, 3, 1, 1, 1>(k, p, s);
-    case CONV_DL_N64:   return launch_conv_t<64,  2, 1, 2, 3, 1, 1, 1>(k, p, s);
-    case CONV_DL_N128:  return launch_conv_t<64,  4, 1, 2, 3, 1, 1, 2>(k, p, s);
-    case CONV_IN_C64:   return launch_conv_t<64,  2, 1, 1, 1, 0, 1, 2>(k, p, s);
-    case CONV_IN_C128:  return launch_conv_t<128, 2, 1, 1, 1, 0, 1, 2>(k, p, s);
-    case CONV_DOWN:     return launch_conv_t<64,  2, 2, 1, 3, 0, 0, 2>(k, p, s);
-    case CONV_UP_EVEN:  return launch_conv_t<128, 4, 1, 1, 2, 1, 0, 4>(k, p, s);
-    case CONV_UP_ODD:   return launch_conv_t<128, 4, 1, 1, 1, 0, 0, 4>(k, p, s);
+    case CONV_EL_C32:   return launch_conv_t<32,  1, 2, 2, 3, 1, 1, 1>(k, p, s, kn);
+    case CONV_EL_C64:   return launch_conv_t<64,  1, 2, 2, 3, 1, 1, 1>(k, p, s, kn);
+    case CONV_EL_C128:  return launch_conv_t<128, 1, 2, 2, 3, 1, 1, 1>(k, p, s, kn);
+    case CONV_DL_N64:   return launch_conv_t<64,  2, 1, 2, 3, 1, 1, 1>(k, p, s, kn);
+    case CONV_DL_N128:  return launch_conv_t<64,  4, 1, 2, 3, 1, 1, 2>(k, p, s, kn);
+    case CONV_IN_C64:   return launch_conv_t<64,  2, 1, 1, 1, 0, 1, 2>(k, p, s, kn);
+    case CONV_IN_C128:  return launch_conv_t<128, 2, 1, 1, 1, 0, 1, 2>(k, p, s, kn);
+    case CONV_DOWN:     return launch_conv_t<64,  2, 2, 1, 3, 0, 0, 2>(k, p, s, kn);
+    case CONV_UP_EVEN:  return launch_conv_t<128, 4, 1, 1, 2, 1, 0, 4>(k, p, s, kn);
+    case CONV_UP_ODD:   return launch_conv_t<128, 4, 1, 1, 1, 0, 0, 4>(k, p, s, kn);
     default:            return hipErrorInvalidValue;
   }
 }

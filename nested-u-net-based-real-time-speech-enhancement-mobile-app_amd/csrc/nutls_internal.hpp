@@ -92,10 +92,23 @@ struct ConvShape {  // static description of a ConvKind
   int cin, nt, stride, tt, kf, padl, epi_ln, g;
 };
 ConvShape conv_shape(ConvKind k);
-// bytes of dynamic LDS one workgroup of `nw` waves needs for this kind at F_out
-size_t conv_lds_bytes(ConvKind k, int f_out, int nw);
-int conv_pick_nw(ConvKind k, int B, int f_out);
-hipError_t launch_conv(ConvKind k, const ConvParams& p, hipStream_t s);
+// Which instantiation of conv_bf16x3_kernel (bf16) / conv_mfma_kernel a launch of B streams x f_out positions runs, and its launch shape: ONE host
+// function owns the rule (kernels.hip conv_choose), launch_conv dispatches on what it returns, nutls_conv_dispatch hands it to the tests.
+// The developer knobs of the rule are host-side only (Engine::conv_knobs, read when a handle is created): they never reach ConvParams or a kernel.
+struct ConvKnobs {
+  int ksplit = 1;            // NUTLS_OFFLINE_KSPLIT=0: the small bf16 launches stay on the 1-wave kernels instead of the K split
+  long long tile_min = -1;   // NUTLS_CONV_TILE_MIN: positions per launch (B * f_out) from which the 128-position tiles run; < 0 (unset): 32 768 for the
+                             // bf16 kernel, 65 536 for the fp32 one.  0: 128-position tiles everywhere; a value no launch reaches: nowhere
+};
+struct ConvChoice {
+  int nw, all;       // template arguments NW and ALL of the instantiation (fp32 kernel: all = 0); (4, 1) is the K split
+  int tile;          // positions per workgroup: 32, or 128 for (4, 0)
+  int threads;
+  unsigned grid;     // workgroups: ceil(B * f_out / tile) -- the last one partly filled where that does not divide
+  size_t lds;        // bytes of dynamic LDS
+};
+ConvChoice conv_choose(ConvKind k, int B, int f_out, bool bf16, const ConvKnobs& kn);
+hipError_t launch_conv(ConvKind k, const ConvParams& p, hipStream_t s, const ConvKnobs& kn);
 
 struct LstmParams {
   const float* x; int x_ld, x_rows, x_cols;   // v[f*x_cols+c] = x[(b*x_rows+f)*x_ld + c]

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "nutls_set_hop_fusion", "nutls_launches_per_hop",
     "nutls_process_block_ragged", "nutls_process_block_ragged_host", "nutls_enhance_block_ragged", "nutls_enhance_block_ragged_host",
     "nutls_stft_block_ragged", "nutls_istft_block_ragged",
+    "nutls_launch_conv_shape", "nutls_conv_dispatch",
 )
 
 
@@ -127,6 +128,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_enhance_block_ragged_host.argtypes = [c.c_void_p, fp, fp, c.c_int, ip, c.c_int]
         lib.nutls_stft_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
         lib.nutls_istft_block_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_conv_dispatch"):
+        ip, lp = c.POINTER(c.c_int), c.POINTER(c.c_longlong)
+        lib.nutls_launch_conv_shape.argtypes = [c.c_void_p, c.c_int, ip, ip]
+        lib.nutls_conv_dispatch.argtypes = [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, ip, ip, ip, lp, lp]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -187,6 +192,36 @@ def host_alloc(shape, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
     weakref.finalize(buf, lib.nutls_host_free, p)      # (the array keeps `buf` alive through its base chain)
     arr[...] = 0.0
     return arr
+
+
+# the kinds of the per-layer conv kernels, in the library's order (csrc/nutls_internal.hpp ConvKind)
+CONV_KINDS = ("el_c32", "el_c64", "el_c128", "dl_n64", "dl_n128", "in_c64", "in_c128", "down", "up_even", "up_odd")
+
+
+def conv_dispatch(kind, batch: int, f_out: int, bf16: bool = True, ksplit: bool = True, tile_min: Optional[int] = None) -> Dict[str, int]:
+    """Which instantiation of the per-layer conv kernels a launch runs and its launch shape (``nutls_conv_dispatch``: the function the
+    library's launches dispatch on; no GPU needed).  ``kind``: a name of ``CONV_KINDS`` or its index; ``batch``: streams of the launch
+    (block mode: utterances x frames); ``bf16``: the bf16-pipe kernel of the block mode, else the fp32-MFMA kernel; ``ksplit`` /
+    ``tile_min``: the developer knobs ``NUTLS_OFFLINE_KSPLIT`` and ``NUTLS_CONV_TILE_MIN`` (None: the defaults) a handle would be created
+    under.  Returns ``{"nw", "all", "tile", "grid", "lds"}``: template arguments NW and ALL, positions per workgroup, workgroups, LDS bytes."""
+    lib = load_library()
+    k = CONV_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    nw, al, tile, grid, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+    _check(lib, lib.nutls_conv_dispatch(k, int(batch), int(f_out), 1 if bf16 else 0, 1 if ksplit else 0, -1 if tile_min is None else int(tile_min),
+                                        ctypes.byref(nw), ctypes.byref(al), ctypes.byref(tile), ctypes.byref(grid), ctypes.byref(lds)))
+    return {"nw": nw.value, "all": al.value, "tile": tile.value, "grid": grid.value, "lds": lds.value}
+
+
+def conv_launches(lib, handle) -> List[Tuple[str, str, int]]:
+    """The conv launches of a handle's per-layer plan (``nutls_launch_conv_shape``): (layer name, kind name, f_out) in issue order."""
+    res = []
+    for i in range(lib.nutls_launches_per_step(handle)):
+        layer, kind, f_out = ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int()
+        _check(lib, lib.nutls_launch_info(handle, i, ctypes.byref(layer), None, None, None))
+        _check(lib, lib.nutls_launch_conv_shape(handle, i, ctypes.byref(kind), ctypes.byref(f_out)))
+        if kind.value >= 0:
+            res.append((layer.value.decode(), CONV_KINDS[kind.value], f_out.value))
+    return res
 
 
 class NutlsEngine:
@@ -476,6 +511,10 @@ class NutlsEngine:
                                                           ctypes.byref(fl), ctypes.byref(by)))
             res.append({"layer": layer.value.decode(), "family": fam.value.decode(), "flops": fl.value, "bytes": by.value})
         return res
+
+    def conv_launches(self) -> List[Tuple[str, str, int]]:
+        """The conv launches of the per-layer plan: (layer name, kind of ``CONV_KINDS``, f_out) in issue order."""
+        return conv_launches(self._lib, self._h)
 
     def fused_plan(self) -> List[Dict[str, object]]:
         """The fused kernel's static schedule: op name and algorithmic flops per stream."""
@@ -929,6 +968,11 @@ class NutlsOffline:
                 _check(self._lib, self._lib.nutls_state_get(self._h, name.encode(), _fptr(a), a.size))
                 return a.reshape(self.utterances, d0.value) if d1.value == 1 else a
         raise ValueError("unknown state tensor: %s" % name)
+
+    def conv_launches(self) -> List[Tuple[str, str, int]]:
+        """The conv launches of the block plan: (layer name, kind of ``CONV_KINDS``, f_out) in issue order; a block of n frames runs each
+        with ``batch = utterances * n`` (``conv_dispatch``)."""
+        return conv_launches(self._lib, self._h)
 
     def reset_utterance(self, u: int):
         """Zero the carried state (and the causal32 attention history) of utterance ``u``: a new utterance starts in that slot."""

@@ -1,4 +1,4 @@
-"""CPU tests behind tests/test_gpu_synthetic_weights.py (no GPU): the export-form quantiser is pinned to the shipped container as data,
+"""CPU tests behind tests/test_gpu_synthetic_weights.py and tests/test_gpu_conv_variants.py (no GPU): the export-form quantiser is pinned to the shipped container as data,
 the float64 oracle is the same function as the float32 one, and every synthetic weight family is well conditioned in the reference
 itself -- the float32 oracle stays within 1/20 of every bound the GPU tests apply against the float64 oracle."""
 import os
@@ -129,8 +129,9 @@ EXCLUDED = {}
 def test_conditioning_cap(family):
     """A condition on the families, not a measurement of any kernel: on every family, for the output of every frame, each of the 18
     traced tensors of every frame and each of the 130 final states of every stream, the float32 oracle lies within 1/20 of the bound
-    the GPU tests apply to that quantity against the float64 oracle; the same for the block-mode inputs of the families that run
-    there.  A family that fails here is changed or dropped -- no bound is widened."""
+    the GPU tests apply to that quantity against the float64 oracle; the same for both block-mode input sets of the families that run
+    there: every output frame of every utterance and all 130 states of every utterance at every frame the block references keep them for.
+    A family that fails here is changed or dropped -- no bound is widened."""
     assert not EXCLUDED.get(family), "nothing is excluded today"
     r64, r32 = WF.reference(family), WF.reference(family, torch.float32)
     assert np.isfinite(r64.out).all() and np.isfinite(r32.out).all()
@@ -151,13 +152,25 @@ def test_conditioning_cap(family):
         print("%s, float container: outputs %.2e x scale, states %.2e x scale (%s)" % (family, out, st[0], st[1]))
         assert out <= WF.CAP * WF.OUT_BOUND
         assert st[0] <= WF.CAP * WF.STATE_BOUND, st
-    if family in WF.BLOCK_FAMILIES:
-        b64, b32 = WF.block_reference(family), WF.block_reference(family, torch.float32)
-        out = max(WF.scaled_rms(b32.out[f], b64.out[f]) for f in range(WF.BLOCK_FRAMES))
-        st = max((WF.scaled_rms(b32.state[n][u], b64.state[n][u]), n, u) for n in WF.state_names() for u in range(2))
-        print("%s, block-mode inputs: outputs %.2e x scale, states %.2e x scale (%s)" % (family, out, st[0], st[1]))
-        assert out <= WF.CAP * WF.OUT_BOUND
+    for U in (2, 3):
+        # both block sets: every output frame of every utterance, and all 130 states of every utterance after every frame the references
+        # keep them for (the end of every block and the mid-block frames tests/test_gpu_conv_variants.py reads through ragged counts)
+        if family not in WF.block_set_families(U):
+            continue
+        b64, b32 = WF.block_reference(family, utterances=U), WF.block_reference(family, torch.float32, utterances=U)
+        frames = b64.out.shape[0]
+        assert frames == (WF.BLOCK_FRAMES if U == 2 else WF.BLOCK3_FRAMES) and b64.out.shape[1] == U
+        assert set(b64.states_at) == set(b32.states_at) == set(WF.block_keep_frames(U)) and frames - 1 in b64.states_at
+        out = max((WF.scaled_rms(b32.out[f, u], b64.out[f, u]), f, u) for f in range(frames) for u in range(U))
+        st = max((WF.scaled_rms(b32.states_at[f][n][u], b64.states_at[f][n][u]), n, f, u)
+                 for f in b64.states_at for n in WF.state_names() for u in range(U))
+        print("%s, block-mode inputs, %d utterances: outputs %.2e x scale (share of the bound %.4f; frame %d, utterance %d), all 130 states after %d "
+              "frames %.2e x scale (share %.4f; %s, frame %d, utterance %d)"
+              % (family, U, out[0], out[0] / WF.OUT_BOUND, out[1], out[2], len(b64.states_at), st[0], st[0] / WF.STATE_BOUND, st[1], st[2], st[3]))
+        assert out[0] <= WF.CAP * WF.OUT_BOUND, out
         assert st[0] <= WF.CAP * WF.STATE_BOUND, st
+        for n in WF.state_names():
+            assert np.array_equal(b64.states_at[frames - 1][n], b64.state[n]), n
 
 
 def test_families_are_what_they_say():

@@ -1,5 +1,6 @@
 """Synthetic weight families, inputs and float64 reference values for the LSTM-variant kernels (a plain helper module: the CPU tests
-of tests/test_weight_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py share it, and its caches) and, in its second
+of tests/test_weight_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py and tests/test_gpu_conv_variants.py share it,
+and its caches) and, in its second
 half (``variant="baseline"``), for the dilated-dense baseline's (tests/test_baseline_families.py, tests/test_gpu_baseline_families.py).
 
 Every family starts from ``synthetic_weights("lstm", SEED, bias_std=0.1, affine_jitter=0.1)`` and is stored as the export stores the
@@ -231,31 +232,84 @@ def block_inputs():
     return x
 
 
+# ---- the block sets of tests/test_gpu_conv_variants.py -------------------------------------------------------------------------------------
+# Per number of utterances U: the blocks the frames are cut into, and which of them are also run RAGGED (block index -> one count per
+# utterance, the longest equal to the block's length so that the launches are the uniform block's): the carried state of utterance u is then
+# taken from frame counts[u] of the block, which is how a test reads states in the middle of a block.
+# U = 3: every dense position count U * n is odd (27, 3, 21), so at F_out = 64 the last 128-position tile of every launch is half filled.  Of
+# block 0 (27 dense streams) the counts (4, 6, 9) sample dense streams 3, 14 and 26: at every F_out <= 64 stream 26 lies in the partly filled
+# last tile of a 128-position launch, and at every F_out >= 8 stream 3 lies in a full one (F_out <= 4: 27 F_out < 128, the launch is one
+# partly filled tile; F_out >= 128: every tile is full).
+BLOCK3_FRAMES = 17
+BLOCK3_FAMILIES = ("plain", "tinyvar", "dead")
+BLOCK_SETS = {2: {"blocks": (17, 1, 9), "ragged": {0: (6, 17), 2: (9, 4)}},
+              3: {"blocks": (9, 1, 7), "ragged": {0: (4, 6, 9), 2: (3, 5, 7)}}}
+
+
+def block_set_inputs(utterances):
+    return block_inputs() if utterances == 2 else block3_inputs()
+
+
+def block_set_families(utterances):
+    return BLOCK_FAMILIES if utterances == 2 else BLOCK3_FAMILIES
+
+
+def block_starts(utterances):
+    blocks = BLOCK_SETS[utterances]["blocks"]
+    return [sum(blocks[:i]) for i in range(len(blocks))]
+
+
+def block_keep_frames(utterances):
+    """The frames after which the block references keep all states: the last frame of every block and the ragged sample frames."""
+    cfg, starts = BLOCK_SETS[utterances], block_starts(utterances)
+    keep = {a + n - 1 for a, n in zip(starts, cfg["blocks"])}
+    for i, counts in cfg["ragged"].items():
+        keep |= {starts[i] + c - 1 for c in counts}
+    return frozenset(keep)
+
+
+@functools.lru_cache(maxsize=None)
+def block3_inputs():
+    """[3, BLOCK3_FRAMES, 256]: utterances 0 and 1 are the first 17 frames of `block_inputs`; utterance 2 is noise of its own draw under a
+    gain that swings between 0.02 and 1 from frame to frame."""
+    x = np.zeros((3, BLOCK3_FRAMES, 256), np.float32)
+    x[:2] = block_inputs()[:, :BLOCK3_FRAMES]
+    rng = np.random.default_rng(SEED + 6)
+    gain = np.float32(0.51 + 0.49 * np.cos(1.3 * np.arange(BLOCK3_FRAMES)))
+    x[2] = 0.25 * np.abs(rng.standard_normal((BLOCK3_FRAMES, 256))) * gain[:, None]
+    x.setflags(write=False)
+    return x
+
+
 class Run:
     """What an oracle run leaves: ``out [frames, B, 256]``, ``trace[name] [frames, B, F, C]``, ``state[name] [B, ...]`` after the last
-    frame -- all float64 numpy, read-only."""
+    frame, ``states_at[f][name] [B, ...]`` after frame f (0-based) for the frames that were asked for -- all float64 numpy, read-only."""
 
-    def __init__(self, out, trace, state):
-        self.out, self.trace, self.state = out, trace, state
-        for a in [out] + list(trace.values()) + list(state.values()):
+    def __init__(self, out, trace, state, states_at=None):
+        self.out, self.trace, self.state, self.states_at = out, trace, state, states_at or {}
+        for a in [out] + list(trace.values()) + list(state.values()) + [a for d in self.states_at.values() for a in d.values()]:
             a.setflags(write=False)
 
 
-def _oracle(blob, x, dtype, trace, variant="lstm", state=None):
-    """x [frames, B, 256] through oracle B in ``dtype``; ``state``: the state tensors to start from (zeros otherwise)"""
+def _oracle(blob, x, dtype, trace, variant="lstm", state=None, keep=()):
+    """x [frames, B, 256] through oracle B in ``dtype``; ``state``: the state tensors to start from (zeros otherwise); ``keep``: frame
+    indices after which all states are kept (``Run.states_at``)"""
     ref = NutlsRef(parse_blob(blob), batch=x.shape[1], dtype=dtype, variant=variant)
     if state is not None:
         for n in state_names(variant):
             assert ref.state[n].shape == state[n].shape, n
             ref.state[n] = torch.from_numpy(np.array(state[n])).to(dtype)
     outs, tr = [], {n: [] for n in traced_names()} if trace else {}
+    states_at = {}
     for f in range(x.shape[0]):
         ref.trace = {} if trace else None
         outs.append(ref.step(x[f]).numpy().astype(np.float64))
         for n in tr:
             tr[n].append(ref.trace[n].numpy().astype(np.float64))
+        if f in keep:
+            states_at[f] = {n: ref.state[n].numpy().astype(np.float64) for n in state_names(variant)}
     state = {n: ref.state[n].numpy().astype(np.float64) for n in state_names(variant)}
-    return Run(np.stack(outs), {n: np.stack(v) for n, v in tr.items()}, state)
+    return Run(np.stack(outs), {n: np.stack(v) for n, v in tr.items()}, state, states_at)
 
 
 @functools.lru_cache(maxsize=None)
@@ -274,9 +328,11 @@ def baseline_continuation(family):
 
 
 @functools.lru_cache(maxsize=None)
-def block_reference(family, dtype=torch.float64):
-    """The block-mode inputs, frame by frame through the oracle (utterances as the batch)."""
-    return _oracle(container(family), np.ascontiguousarray(block_inputs().transpose(1, 0, 2)), dtype, trace=False)
+def block_reference(family, dtype=torch.float64, utterances=2):
+    """The block-mode inputs (two utterances, or the three of `block3_inputs`), frame by frame through the oracle (utterances as the
+    batch); all states are kept after the frames of `block_keep_frames`."""
+    x = block_set_inputs(utterances)
+    return _oracle(container(family), np.ascontiguousarray(x.transpose(1, 0, 2)), dtype, trace=False, keep=block_keep_frames(utterances))
 
 
 # ---- measures ----------------------------------------------------------------------------------------------------------------------
