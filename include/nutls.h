@@ -272,6 +272,75 @@ int nutls_enhance_block_ragged_host(nutls_handle* h, const float* pcm_in, float*
 int nutls_stft_block_ragged(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, const int* hops, void* stream);
 int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
 
+/* ---- PCM gateway: the callers' sample rate and sample type, converted on the device -----------------------------------------
+ * Every waveform entry above takes and returns float32 samples at exactly 16 kHz (the reference refuses anything else:
+ * interpreter_proposed.py:384-385); telephony delivers 16-bit samples at 8 kHz, capture devices and WebRTC 48 kHz, the phone app 16-bit PCM
+ * (AudioFormat.ENCODING_PCM_16BIT).  A handle is told its callers' format once; the _pcm entries below then take and return that audio and
+ * keep the resampler state per stream, next to the state the library already owns.
+ *
+ * Format: rate_hz = 8000, 16000, 32000 or 48000; sample_format = NUTLS_PCM_F32 or NUTLS_PCM_S16.  A hop stays 16 ms at every rate:
+ * S = 256 * rate / 16000 samples (128, 256, 512, 768).  Buffers are [B, S] (hops) / [utterances, n_hops * S] (blocks) of the sample type,
+ * rows contiguous, base pointer 16-byte aligned.  A handle starts at 16000 / NUTLS_PCM_F32.  nutls_set_pcm_format may be called between any
+ * two hops; it zeroes every stream's resampler history (as a mode switch starts a new history) and synchronises the device.  Another rate or
+ * format is NUTLS_ERR_ARG and changes nothing.  The format applies to the _pcm entries ONLY: nutls_enhance_hop, nutls_enhance_block,
+ * nutls_stft_hop / _block, nutls_istft_hop / _block and their variants keep taking float32 at 16 kHz, whatever was set.
+ * At 16000 / NUTLS_PCM_F32 the _pcm entries ARE the plain entries: same code path, same bits, no extra launch, no delay.
+ *
+ * Samples: int16 -> float is s / 32768 (exact); float -> int16 is y * 32768 rounded to nearest even and clamped to -32768 .. 32767, NaN -> 0.
+ * The float that is quantised is bit for bit the value the NUTLS_PCM_F32 format returns.
+ *
+ * Rates: q = max(rate, 16000) / min(rate, 16000) = 2 or 3.  One linear-phase FIR prototype p[0 .. 2 K q] per rate, K = 24: a Kaiser-windowed
+ * sinc (beta 8) with its cutoff at the LOWER rate's Nyquist frequency, designed in double when needed, normalised to sum 1 and rounded to
+ * fp32 once -- nutls_pcm_filter returns exactly the numbers the kernels use (in units of that Nyquist frequency: within 0.01 dB up to 0.85,
+ * -6 dB at 1.0, at least 80 dB down from 1.15; symmetric to the bit; 2 K q + 1 taps, the single tap 1.0 for 16000).  The conversion is plain
+ * causal filtering of a stream's concatenated samples from a zero state (samples before the first are zeros):
+ *   rate reduction by q:  y[m] = sum_j p[j] x[q m - j]                          (scipy: upfirdn(p, x, 1, q))
+ *   rate increase by q:   zero-stuff by q, then filter with q p                 (scipy: upfirdn(q p, x, q, 1))
+ * both truncated to the input's length times the ratio.  A rate above 16 kHz is reduced on the way in and increased on the way out, 8 kHz
+ * the other way round.  Each direction delays by K samples of the lower rate: nutls_pcm_delay_samples = 2 K max(1, rate / 16000) samples at
+ * the caller's rate for the two together (0 at 16000); the one-hop lag of nutls_enhance_hop stays on top of it.
+ * Band limit: a 32 or 48 kHz caller gets back audio band-limited to 8 kHz -- that is what the model produces.  Passing the upper band around
+ * the model is out of scope.
+ *
+ * State: per stream (utterance) and direction the library keeps the filter's last 2 K q input samples, outside the signature's tensors.
+ * nutls_reset(h, b) zeroes stream b's (-1: everybody's).  A held stream (active[b] == 0) keeps it as it is -- neither kernel touches it -- and
+ * its row of pcm_out is zeros; its row of pcm_in is not read.  An offline handle carries it from block to block.  Every output sample is the
+ * same sum, in the same order (taps ascending, one fp32 FMA each; the zero-stuffed terms skipped), over the same values wherever the hop or
+ * block boundary falls: the two halves are bit-exact across every cut of a stream, between ticks 0, 3, 4 and ticks 0, 1, 2, and between the
+ * hop entries of a streaming handle and the block entries of an offline one.
+ *
+ * Where: the hop entries wherever nutls_enhance_hop works (both variants, every mode, hop fusion on or off); the masked ones wherever
+ * nutls_enhance_hop_active works, with the same refusals (checked before anything is converted: a refused call changes nothing).  Each
+ * _pcm entry decodes into a library buffer, calls that plain entry on library buffers and encodes: two small launches more per hop or block.
+ * An offline handle gets NUTLS_ERR_ARG from the hop entries, a streaming handle from the block entries.
+ * The _host entries copy the raw samples (pageable or nutls_host_alloc) into library buffers, run the pipeline and copy back; they
+ * synchronise like their float twins -- int16 moves half the bytes over the link.  nutls_enhance_hop_pcm_host_active hands its mask on as
+ * a device mask (see nutls_step_active on nutls_state_set and masks the host has not seen).  No zero-copy reads of pinned PCM, no ragged
+ * blocks in the callers' format: nutls_enhance_block_ragged stays at float32 and 16 kHz. */
+#define NUTLS_PCM_F32 0   /* float32, unit scale (what nutls_enhance_hop takes) */
+#define NUTLS_PCM_S16 1   /* int16, little endian; 32768 = 1.0 */
+int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);
+int nutls_pcm_hop_samples(nutls_handle* h);     /* S = 256 * rate / 16000: 128, 256, 512, 768 */
+int nutls_pcm_delay_samples(nutls_handle* h);   /* delay of the two rate conversions together, in samples at the caller's rate */
+int nutls_pcm_filter_taps(int rate_hz);         /* host only, no handle: 2 K q + 1; 1 for 16000; -1 for an unsupported rate */
+int nutls_pcm_filter(int rate_hz, float* taps, int n);   /* host only: the fp32 prototype filter the kernels use; n = nutls_pcm_filter_taps */
+/* Streaming handles.  pcm_in / pcm_out: DEVICE [B, S] of the handle's sample type (HOST in the _host entries); `active` as in
+ * nutls_enhance_hop_active (DEVICE [B] bytes, HOST in the _host entry; NULL = the entry without the mask); asynchronous on `stream`. */
+int nutls_enhance_hop_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode, void* stream);
+int nutls_enhance_hop_pcm_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream);
+int nutls_enhance_hop_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode);
+int nutls_enhance_hop_pcm_host_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode);
+/* The two halves on their own (testing, custom models), as nutls_stft_hop / nutls_istft_hop are: the callers' format <-> DEVICE [B, 256]
+ * float32 at 16 kHz.  `active`: DEVICE mask or NULL; a held row of the output is zeros.  Any streaming handle. */
+int nutls_pcm_decode_hop(nutls_handle* h, const void* pcm_in, float* hop_out, const unsigned char* active, void* stream);
+int nutls_pcm_encode_hop(nutls_handle* h, const float* hop_in, void* pcm_out, const unsigned char* active, void* stream);
+/* Offline handles (nutls_create_offline, nutls_create_offline_batch): DEVICE [utterances, n_hops * S] (HOST in the _host entry),
+ * 1 <= n_hops <= max_frames; the 16 kHz side of the halves is [utterances, n_hops * 256] float32. */
+int nutls_enhance_block_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode, void* stream);
+int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode);
+int nutls_pcm_decode_block(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, void* stream);
+int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, void* stream);
+
 /* Library-owned device staging buffers [B,256]; stepping on them avoids the D2D copies and lets
  * the captured hipGraph run with no per-call parameter update. */
 int nutls_io_buffers(nutls_handle* h, float** mag_in, float** mag_out);

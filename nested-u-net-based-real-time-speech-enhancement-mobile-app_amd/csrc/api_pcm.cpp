@@ -1,0 +1,298 @@
+// PCM gateway of the C ABI (include/nutls.h, "PCM gateway"): a handle is told its callers' sample rate and sample type once
+// (nutls_set_pcm_format), and the _pcm entries take and return that audio -- hop by hop with masks on streaming handles, block by block on
+// offline ones.  Every entry here decodes into a library float32 buffer at 16 kHz, calls the existing entry (nutls_enhance_hop,
+// nutls_enhance_hop_active, nutls_enhance_block) on library buffers and encodes: the model path, the masks, hop fusion and the state
+// coherence are that code, not copies of it.  At 16000 / float32 the entries ARE the plain ones (forwarded before anything else happens).
+// The kernels: pcm.hip.
+#include "engine.hpp"
+
+using namespace nutls;
+
+namespace {
+
+bool plain_format(const Engine* e) { return e->pcm.rate == 16000 && e->pcm.fmt == NUTLS_PCM_F32; }
+int hop_samples(const Engine* e) { return NUTLS_FRAME_STEP / 16 * (e->pcm.rate / 1000); }      // 256 * rate / 16000
+size_t sample_bytes(const Engine* e) { return e->pcm.fmt == NUTLS_PCM_S16 ? sizeof(short) : sizeof(float); }
+int max_hops(const Engine* e) { return e->offline ? e->offline : 1; }
+
+int upload_taps(Engine* e) {
+  const std::vector<float> p = pcm_design(e->pcm.rate);
+  HIP_TRY(hipMemcpy(e->pcm.taps, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
+  return NUTLS_OK;
+}
+
+// Buffers of the gateway, allocated when an entry first needs them (every later call: nothing happens).
+int pcm_init(Engine* e) {
+  PcmState& st = e->pcm;
+  if (st.ready) return NUTLS_OK;
+  st.rows = e->offline ? e->outt : e->B;
+  const size_t hist = static_cast<size_t>(st.rows) * kPcmMaxHist;
+  const size_t wave = static_cast<size_t>(st.rows) * max_hops(e) * NUTLS_FRAME_STEP;
+  int rc;
+  if ((rc = dev_alloc_once(e, static_cast<size_t>(2 * kPcmK * kPcmMaxQ + 1), &st.taps, false)) || (rc = dev_alloc_once(e, hist, &st.hist_dec[0], true)) ||
+      (rc = dev_alloc_once(e, hist, &st.hist_dec[1], true)) || (rc = dev_alloc_once(e, hist, &st.hist_enc[0], true)) ||
+      (rc = dev_alloc_once(e, hist, &st.hist_enc[1], true)) || (rc = dev_alloc_once(e, wave, &st.f_in, true)) ||
+      (rc = dev_alloc_once(e, wave, &st.f_out, true)) || (rc = upload_taps(e)))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());      // the zeroes are in place before a caller's stream reads them
+  st.ready = true;
+  return NUTLS_OK;
+}
+
+int zero_histories(Engine* e, int idx) {
+  PcmState& st = e->pcm;
+  if (!st.ready) return NUTLS_OK;
+  for (float* p : {st.hist_dec[0], st.hist_dec[1], st.hist_enc[0], st.hist_enc[1]}) {
+    if (idx < 0) HIP_TRY(hipMemset(p, 0, static_cast<size_t>(st.rows) * kPcmMaxHist * sizeof(float)));
+    else HIP_TRY(hipMemset(p + static_cast<size_t>(idx) * kPcmMaxHist, 0, kPcmMaxHist * sizeof(float)));
+  }
+  return NUTLS_OK;
+}
+
+// One launch of a half.  A block call (offline handle) flips the history buffers; a hop call (streaming handle) works in place on buffer 0.
+int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s) {
+  PcmState& st = e->pcm;
+  const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
+  HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  st.dec_par = nxt;
+  return NUTLS_OK;
+}
+
+int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s) {
+  PcmState& st = e->pcm;
+  const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
+  HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  st.enc_par = nxt;
+  return NUTLS_OK;
+}
+
+// the _host entries' staging of the callers' samples
+int raw_init(Engine* e) {
+  const size_t bytes = static_cast<size_t>(e->pcm.rows) * max_hops(e) * kPcmMaxHop * sizeof(float);
+  if (int rc = dev_alloc_once(e, bytes, &e->pcm.raw_in, false)) return rc;
+  return dev_alloc_once(e, bytes, &e->pcm.raw_out, false);
+}
+
+int dc_ok(int dc_mode, const char* who) {
+  if (dc_mode != NUTLS_DC_EDGE && dc_mode != NUTLS_DC_ZERO) return fail(NUTLS_ERR_ARG, std::string(who) + ": dc_mode must be NUTLS_DC_EDGE or NUTLS_DC_ZERO");
+  return NUTLS_OK;
+}
+
+// what every hop entry checks first: pointers, then the kind of handle
+int hop_args(nutls_handle* h, bool pointers_ok, const char* who) {
+  if (!h || !pointers_ok) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  if (h->eng.offline)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": offline handle (nutls_create_offline): it takes the callers' samples block by block through nutls_enhance_block_pcm");
+  return NUTLS_OK;
+}
+
+int block_args(nutls_handle* h, bool pointers_ok, int n_hops, const char* who) {
+  if (!h || !pointers_ok) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  const Engine* e = &h->eng;
+  if (!e->offline)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": not an offline handle (nutls_create_offline); a streaming handle takes the callers' samples hop by hop through nutls_enhance_hop_pcm");
+  if (n_hops < 1 || n_hops > e->offline) return fail(NUTLS_ERR_ARG, std::string(who) + ": n_hops out of range (1 .. max_frames)");
+  return NUTLS_OK;
+}
+
+// Refusals of a converting hop come before the decode: a refused call leaves the resampler histories where they were.
+int hop_refusals(nutls_handle* h, const unsigned char* active, int dc_mode, const char* who) {
+  if (int rc = dc_ok(dc_mode, who)) return rc;
+  if (active)
+    if (int rc = check_active(&h->eng, who)) return rc;
+  return NUTLS_OK;
+}
+
+// decode -> nutls_enhance_hop(_active) on the library's float buffers -> encode (active: device mask or null)
+int hop_device(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, active, 1, s)) return rc;
+  if (int rc = nutls_enhance_hop_active(h, e->pcm.f_in, e->pcm.f_out, active, dc_mode, stream)) return rc;
+  return encode_launch(e, e->pcm.f_out, pcm_out, active, 1, s);
+}
+
+// The callers' samples to the library's staging, hop_device on the library's stream, the results back, one synchronisation (active: HOST mask
+// or null).  The mask is handed on as a device mask: the library does not follow it through nutls_state_set's bookkeeping as the float _host
+// entries do (nutls.h, nutls_step_active: the more expensive launches then last until one call steps all streams).
+int hop_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode) {
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  if (int rc = raw_init(e)) return rc;
+  const unsigned char* d_act = nullptr;
+  if (active) {
+    if (int rc = dev_alloc_once(e, static_cast<size_t>(e->B), &e->pcm.d_active, false)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->pcm.d_active, active, static_cast<size_t>(e->B), hipMemcpyHostToDevice, e->stream));
+    d_act = e->pcm.d_active;
+  }
+  const size_t bytes = static_cast<size_t>(e->B) * hop_samples(e) * sample_bytes(e);
+  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = hop_device(h, e->pcm.raw_in, e->pcm.raw_out, d_act, dc_mode, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return NUTLS_OK;
+}
+
+int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, nullptr, n_hops, s)) return rc;
+  if (int rc = nutls_enhance_block(h, e->pcm.f_in, e->pcm.f_out, n_hops, dc_mode, stream)) return rc;
+  return encode_launch(e, e->pcm.f_out, pcm_out, nullptr, n_hops, s);
+}
+
+}  // namespace
+
+namespace nutls {
+
+int pcm_reset(Engine* e, int idx) { return zero_histories(e, idx); }
+
+}  // namespace nutls
+
+extern "C" {
+
+// ---- the format of a handle ---------------------------------------------------------------------------------------------------------------
+int nutls_pcm_filter_taps(int rate_hz) {
+  const int q = pcm_ratio(rate_hz);
+  return q == 0 ? -1 : q == 1 ? 1 : 2 * kPcmK * q + 1;
+}
+
+int nutls_pcm_filter(int rate_hz, float* taps, int n) {
+  if (!taps) return fail(NUTLS_ERR_ARG, "nutls_pcm_filter: null pointer");
+  const int want = nutls_pcm_filter_taps(rate_hz);
+  if (want < 0) return fail(NUTLS_ERR_ARG, "nutls_pcm_filter: rate must be 8000, 16000, 32000 or 48000");
+  if (n != want) return fail(NUTLS_ERR_ARG, "nutls_pcm_filter: the filter of " + std::to_string(rate_hz) + " Hz has " + std::to_string(want) + " taps (nutls_pcm_filter_taps)");
+  const std::vector<float> p = pcm_design(rate_hz);
+  for (int i = 0; i < n; ++i) taps[i] = p[i];
+  return NUTLS_OK;
+}
+
+int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: null handle");
+  if (!pcm_ratio(rate_hz)) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: rate must be 8000, 16000, 32000 or 48000");
+  if (sample_format != NUTLS_PCM_F32 && sample_format != NUTLS_PCM_S16)
+    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: sample format must be NUTLS_PCM_F32 or NUTLS_PCM_S16");
+  Engine* e = &h->eng;
+  const bool to_plain = rate_hz == 16000 && sample_format == NUTLS_PCM_F32;
+  if (!e->pcm.ready && to_plain) {      // nothing has been converted yet and nothing will be
+    e->pcm.rate = rate_hz;
+    e->pcm.fmt = sample_format;
+    return NUTLS_OK;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // queued conversions still read the taps and histories that change below
+  e->pcm.rate = rate_hz;
+  e->pcm.fmt = sample_format;
+  if (!e->pcm.ready) {
+    if (int rc = pcm_init(e)) return rc;      // (uploads the taps, zeroes the histories)
+  } else {
+    if (int rc = upload_taps(e)) return rc;
+    if (int rc = zero_histories(e, -1)) return rc;      // a format switch starts a new history for every stream
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return NUTLS_OK;
+}
+
+int nutls_pcm_hop_samples(nutls_handle* h) { return h ? hop_samples(&h->eng) : fail(NUTLS_ERR_ARG, "nutls_pcm_hop_samples: null handle"); }
+
+int nutls_pcm_delay_samples(nutls_handle* h) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_pcm_delay_samples: null handle");
+  const int rate = h->eng.pcm.rate;
+  return rate == 16000 ? 0 : 2 * kPcmK * (rate > 16000 ? rate / 16000 : 1);
+}
+
+// ---- streaming handles ----------------------------------------------------------------------------------------------------------------------
+int nutls_enhance_hop_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode, void* stream) {
+  if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm")) return rc;
+  if (plain_format(&h->eng)) return nutls_enhance_hop(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode, stream);
+  if (int rc = hop_refusals(h, nullptr, dc_mode, "nutls_enhance_hop_pcm")) return rc;
+  return hop_device(h, pcm_in, pcm_out, nullptr, dc_mode, stream);
+}
+
+int nutls_enhance_hop_pcm_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_active")) return rc;
+  if (!active) return nutls_enhance_hop_pcm(h, pcm_in, pcm_out, dc_mode, stream);
+  if (plain_format(&h->eng)) return nutls_enhance_hop_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode, stream);
+  if (int rc = hop_refusals(h, active, dc_mode, "nutls_enhance_hop_pcm_active")) return rc;
+  return hop_device(h, pcm_in, pcm_out, active, dc_mode, stream);
+}
+
+int nutls_enhance_hop_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode) {
+  if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_host")) return rc;
+  if (plain_format(&h->eng)) return nutls_enhance_hop_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode);
+  if (int rc = hop_refusals(h, nullptr, dc_mode, "nutls_enhance_hop_pcm_host")) return rc;
+  return hop_host(h, pcm_in, pcm_out, nullptr, dc_mode);
+}
+
+int nutls_enhance_hop_pcm_host_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode) {
+  if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_host_active")) return rc;
+  if (!active) return nutls_enhance_hop_pcm_host(h, pcm_in, pcm_out, dc_mode);
+  if (plain_format(&h->eng))
+    return nutls_enhance_hop_host_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode);
+  if (int rc = hop_refusals(h, active, dc_mode, "nutls_enhance_hop_pcm_host_active")) return rc;
+  return hop_host(h, pcm_in, pcm_out, active, dc_mode);
+}
+
+// The two halves on their own (at 16000 / float32: copies).  They need no model, so a mask is taken on every streaming handle.
+int nutls_pcm_decode_hop(nutls_handle* h, const void* pcm_in, float* hop_out, const unsigned char* active, void* stream) {
+  if (int rc = hop_args(h, pcm_in && hop_out, "nutls_pcm_decode_hop")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return decode_launch(e, pcm_in, hop_out, active, 1, static_cast<hipStream_t>(stream));
+}
+
+int nutls_pcm_encode_hop(nutls_handle* h, const float* hop_in, void* pcm_out, const unsigned char* active, void* stream) {
+  if (int rc = hop_args(h, hop_in && pcm_out, "nutls_pcm_encode_hop")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return encode_launch(e, hop_in, pcm_out, active, 1, static_cast<hipStream_t>(stream));
+}
+
+// ---- offline handles --------------------------------------------------------------------------------------------------------------------------
+int nutls_enhance_block_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode, void* stream) {
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_pcm")) return rc;
+  if (plain_format(&h->eng)) return nutls_enhance_block(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode, stream);
+  if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm")) return rc;
+  return block_device(h, pcm_in, pcm_out, n_hops, dc_mode, stream);
+}
+
+int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode) {
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_pcm_host")) return rc;
+  if (plain_format(&h->eng)) return nutls_enhance_block_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode);
+  if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm_host")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  if (int rc = raw_init(e)) return rc;
+  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * hop_samples(e) * sample_bytes(e);
+  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = block_device(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, dc_mode, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return NUTLS_OK;
+}
+
+int nutls_pcm_decode_block(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, void* stream) {
+  if (int rc = block_args(h, pcm_in && wave_out, n_hops, "nutls_pcm_decode_block")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return decode_launch(e, pcm_in, wave_out, nullptr, n_hops, static_cast<hipStream_t>(stream));
+}
+
+int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, void* stream) {
+  if (int rc = block_args(h, wave_in && pcm_out, n_hops, "nutls_pcm_encode_block")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return encode_launch(e, wave_in, pcm_out, nullptr, n_hops, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -186,6 +186,7 @@ int nutls_reset(nutls_handle* h, int stream_idx) {
       else HIP_TRY(hipMemset(p + static_cast<size_t>(NUTLS_FRAME_STEP) * utt, 0, hop));
     }
   }
+  if (int rcp = pcm_reset(e, utt)) return rcp;      // PCM gateway: the stream's / utterance's resampler histories
   HIP_TRY(hipDeviceSynchronize());
   return NUTLS_OK;
 }

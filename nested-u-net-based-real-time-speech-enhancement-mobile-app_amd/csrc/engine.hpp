@@ -1,5 +1,5 @@
 // What the host translation units behind the C ABI share -- engine.cpp (the engine) and api_stream.cpp, api_block.cpp, api_state.cpp,
-// api_profile.cpp (the entry points): the Engine inside a handle, the small structs it is made of, the one error slot and the internal
+// api_profile.cpp, api_pcm.cpp (the entry points): the Engine inside a handle, the small structs it is made of, the one error slot and the internal
 // functions that cross a file boundary.  Host only, like fused_host.hpp: no kernel translation unit includes it.
 #pragma once
 
@@ -14,6 +14,7 @@
 #include "nutls_internal.hpp"
 #include "fused_host.hpp"
 #include "ragged.hpp"
+#include "pcm.hpp"
 
 namespace nutls {
 
@@ -188,6 +189,8 @@ struct Engine {
   int ochunks = 0;                      // 0 = chosen from the block length
   int* d_counts = nullptr;              // [outt] ints: device copy of the counts of the _host entries of the ragged block calls (nutls_process_block_ragged_host)
   std::vector<int> ogroup;              // launch index of plan_off -> group (a group ends with an LSTM)
+  // ---- PCM gateway ---------------------------------------------------------------------------
+  PcmState pcm;          // the callers' sample rate and type (nutls_set_pcm_format) and the resampler histories of the _pcm entries
 
   ~Engine() {
     for (int i = 0; i < 2; ++i)
@@ -234,6 +237,10 @@ int check_hop_fusion(const Engine* e, const char* who);
 
 // ---- api_block.cpp ---------------------------------------------------------------------------
 int build_offline_plan(Engine* e);
+
+// ---- api_pcm.cpp -----------------------------------------------------------------------------
+// nutls_reset: zero the resampler histories of row `idx` (stream / utterance; < 0: every row's) where they exist
+int pcm_reset(Engine* e, int idx);
 
 }  // namespace nutls
 

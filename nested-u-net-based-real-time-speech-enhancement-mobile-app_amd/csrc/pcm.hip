@@ -1,0 +1,242 @@
+// PCM gateway: the callers' samples (float32 or int16 at 8 / 16 / 32 / 48 kHz) to and from the library's float32 at 16 kHz (nutls_set_pcm_format).
+//
+// Two kernels, decode and encode, each one 256-thread workgroup per (row, hop) -- row = stream of a streaming handle, utterance of an offline
+// one; the hop entries launch them with one hop per row, the block entries with n_hops.  Both run the same body:
+//   1. the prototype p[0 .. 2 K q] and the hop with its left context (the last 2 K q samples in front of it for a rate reduction, the last 2 K
+//      for a rate increase) go to LDS as float32, 16 bytes per lane and load (8 int16 or 4 float32).  The context of a row's first hop comes
+//      from the history the handle keeps, that of the later hops of a block straight from the row;
+//   2. the workgroup of a row's last hop writes the new history: the last samples of what it has just staged;
+//   3. every output sample is ONE chain of fp32 FMAs over the prototype's taps in ascending order, from 0 (pcm_fir: the zero-stuffed terms of a
+//      rate increase are skipped by polyphase indexing, the rest keep their order).  The chain of an output sample does not depend on where
+//      the sample lies in its hop, in its block or in which entry runs it: results are bit-exact across every cut of a stream;
+//   4. the hop leaves through LDS in 16-byte stores (float32 -> int16: y * 32768 rounded to nearest even, clamped, NaN -> 0).
+// A held row (active[row] == 0) returns before 1.: its history is neither read nor written, its output hop is zeros.
+// Cost: 256 * 145 FMAs per stream and hop at most (48 kHz decode); the launch, not the arithmetic, is what a hop pays for.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "pcm.hpp"
+
+namespace nutls {
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kThreads = 256;
+
+template <int Q>
+struct Rate {
+  static constexpr int k = Q == 1 ? 0 : kPcmK;      // 16 kHz: the single tap 1.0, no delay
+  static constexpr int taps = 2 * k * Q + 1;
+};
+
+// ---- one output sample --------------------------------------------------------------------------------------------------------------------
+// x: the staged samples in LDS, x[0] = the oldest sample of the left context (hist samples), x[hist] = the hop's first.
+// DOWN (rate reduction by Q):  y[n] = sum_j p[j] x[Q n - j],                j = 0 .. 2 K Q
+// UP   (rate increase by Q):   z[n] = Q sum_i p[r + Q i] x[m - i],  n = Q m + r,  i = 0 .. 2 K (r = 0) or 2 K - 1   (zero-stuffing, then Q p)
+template <int Q, bool UP>
+__device__ __forceinline__ float pcm_fir(const float* p, const float* x, int n) {
+  constexpr int K = Rate<Q>::k;
+  float acc = 0.f;
+  if constexpr (!UP) {
+    const float* at = x + 2 * K * Q + Q * n;
+#pragma unroll 8
+    for (int j = 0; j <= 2 * K * Q; ++j) acc = fmaf(p[j], at[-j], acc);
+    return acc;
+  } else {
+    const int m = n / Q, r = n - m * Q;
+    const float* at = x + 2 * K + m;
+    const float* pr = p + r;
+#pragma unroll 8
+    for (int i = 0; i < 2 * K; ++i) acc = fmaf(pr[Q * i], at[-i], acc);
+    if (r == 0) acc = fmaf(p[2 * K * Q], at[-2 * K], acc);
+    return acc * static_cast<float>(Q);
+  }
+}
+
+// ---- samples <-> LDS floats, 16 bytes per lane ----------------------------------------------------------------------------------------------
+// (src / dst 16-byte aligned, count a multiple of 8)
+__device__ __forceinline__ void stage_in(const float* src, float* lds, int count, int tid) {
+  for (int i = tid; i < count / 4; i += kThreads) reinterpret_cast<f32x4*>(lds)[i] = reinterpret_cast<const f32x4*>(src)[i];
+}
+__device__ __forceinline__ void stage_in(const short* src, float* lds, int count, int tid) {
+  for (int i = tid; i < count / 8; i += kThreads) {
+    const s16x8 v = reinterpret_cast<const s16x8*>(src)[i];
+    f32x4 lo, hi;
+    for (int k = 0; k < 4; ++k) {
+      lo[k] = static_cast<float>(v[k]) * (1.f / 32768.f);      // exact
+      hi[k] = static_cast<float>(v[4 + k]) * (1.f / 32768.f);
+    }
+    reinterpret_cast<f32x4*>(lds)[2 * i] = lo;
+    reinterpret_cast<f32x4*>(lds)[2 * i + 1] = hi;
+  }
+}
+
+__device__ __forceinline__ short to_s16(float y) {
+  const float v = rintf(y * 32768.f);      // round to nearest even
+  if (v != v) return 0;
+  return static_cast<short>(static_cast<int>(fminf(fmaxf(v, -32768.f), 32767.f)));
+}
+__device__ __forceinline__ void stage_out(const float* lds, float* dst, int count, int tid) {
+  for (int i = tid; i < count / 4; i += kThreads) reinterpret_cast<f32x4*>(dst)[i] = reinterpret_cast<const f32x4*>(lds)[i];
+}
+__device__ __forceinline__ void stage_out(const float* lds, short* dst, int count, int tid) {
+  for (int i = tid; i < count / 8; i += kThreads) {
+    const f32x4 lo = reinterpret_cast<const f32x4*>(lds)[2 * i], hi = reinterpret_cast<const f32x4*>(lds)[2 * i + 1];
+    s16x8 v;
+    for (int k = 0; k < 4; ++k) {
+      v[k] = to_s16(lo[k]);
+      v[4 + k] = to_s16(hi[k]);
+    }
+    reinterpret_cast<s16x8*>(dst)[i] = v;
+  }
+}
+__device__ __forceinline__ void zero_out(float* dst, int count, int tid) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = tid; i < count / 4; i += kThreads) reinterpret_cast<f32x4*>(dst)[i] = z;
+}
+__device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = tid; i < count / 8; i += kThreads) reinterpret_cast<s16x8*>(dst)[i] = z;
+}
+
+// ---- one hop of one row: NIN samples in, NIN / Q (DOWN) or NIN * Q (UP) out --------------------------------------------------------------------
+template <int Q, bool UP, int NIN, typename TI, typename TO>
+__device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                        int n_hops) {
+  constexpr int K = Rate<Q>::k;
+  constexpr int HIST = UP ? 2 * K : 2 * K * Q;      // samples of left context
+  constexpr int NOUT = UP ? NIN * Q : NIN / Q;
+  static_assert(HIST <= kPcmMaxHist && HIST <= NIN && NIN <= kPcmMaxHop && NOUT <= kPcmMaxHop, "staging sizes");
+  static_assert(HIST % 8 == 0 && NIN % 8 == 0 && NOUT % 8 == 0, "16-byte accesses");
+  __shared__ __attribute__((aligned(16))) float s_x[kPcmMaxHist + kPcmMaxHop];
+  __shared__ __attribute__((aligned(16))) float s_y[kPcmMaxHop];
+  __shared__ float s_p[Rate<kPcmMaxQ>::taps];
+  const int t = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
+  TO* const dst = out + (static_cast<size_t>(row) * n_hops + t) * NOUT;
+  if (active && !active[row]) {      // (the whole workgroup: the flag is per row)
+    zero_out(dst, NOUT, tid);
+    return;
+  }
+  const TI* const src = in + (static_cast<size_t>(row) * n_hops + t) * NIN;
+  for (int i = tid; i < Rate<Q>::taps; i += kThreads) s_p[i] = taps[i];
+  if constexpr (HIST > 0) {
+    if (t > 0) stage_in(src - HIST, s_x, HIST, tid);
+    else stage_in(hist_in + static_cast<size_t>(row) * kPcmMaxHist, s_x, HIST, tid);
+  }
+  stage_in(src, s_x + HIST, NIN, tid);
+  __syncthreads();
+  if constexpr (HIST > 0) {
+    // the history the next call starts from.  hist_out may be hist_in only where this workgroup is also the one that read it (n_hops == 1)
+    if (t == n_hops - 1) stage_out(s_x + NIN, hist_out + static_cast<size_t>(row) * kPcmMaxHist, HIST, tid);
+  }
+  for (int n = tid; n < NOUT; n += kThreads) s_y[n] = pcm_fir<Q, UP>(s_p, s_x, n);
+  __syncthreads();
+  stage_out(s_y, dst, NOUT, tid);
+}
+
+// caller samples -> 16 kHz float32: a rate above 16 kHz is reduced, 8 kHz is doubled
+template <int Q, bool UP, typename TI>
+__global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
+                                                              const unsigned char* active, int n_hops) {
+  pcm_hop<Q, UP, UP ? 256 / Q : 256 * Q, TI, float>(in, out, taps, hist_in, hist_out, active, n_hops);
+}
+
+// 16 kHz float32 -> caller samples
+template <int Q, bool UP, typename TO>
+__global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
+                                                              const unsigned char* active, int n_hops) {
+  pcm_hop<Q, UP, 256, float, TO>(in, out, taps, hist_in, hist_out, active, n_hops);
+}
+
+template <int Q, bool UP, typename T>
+hipError_t decode_as(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active, int rows,
+                     int n_hops, hipStream_t s) {
+  hipLaunchKernelGGL((pcm_decode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out,
+                     active, n_hops);
+  return hipGetLastError();
+}
+
+template <int Q, bool UP, typename T>
+hipError_t encode_as(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active, int rows,
+                     int n_hops, hipStream_t s) {
+  hipLaunchKernelGGL((pcm_encode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out,
+                     active, n_hops);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+int pcm_ratio(int rate_hz) {
+  switch (rate_hz) {
+    case 16000: return 1;
+    case 8000: case 32000: return 2;
+    case 48000: return 3;
+    default: return 0;
+  }
+}
+
+std::vector<float> pcm_design(int rate_hz) {
+  const int q = pcm_ratio(rate_hz);
+  if (q == 0) return {};
+  if (q == 1) return {1.0f};
+  const int half = kPcmK * q, n = 2 * half + 1;
+  const double pi = 3.14159265358979323846, beta = 8.0;
+  auto bessel_i0 = [](double x) {      // sum_k ((x / 2)^k / k!)^2
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 64; ++k) {
+      term *= (x / 2) / k;
+      sum += term * term;
+    }
+    return sum;
+  };
+  std::vector<double> p(n);
+  double total = 0.0;
+  for (int i = 0; i <= half; ++i) {      // one half, mirrored: symmetric to the bit
+    const double d = static_cast<double>(i - half);
+    // (the sinc's zeros -- every q-th tap off the centre -- are exact zeros, not sin(k pi) of a double: the prototype is a Nyquist filter)
+    const double sinc = i == half ? 1.0 : (half - i) % q == 0 ? 0.0 : std::sin(pi * d / q) / (pi * d / q);
+    const double r = d / half;
+    const double v = sinc / q * bessel_i0(beta * std::sqrt(1.0 - r * r)) / bessel_i0(beta);
+    p[i] = p[n - 1 - i] = v;
+  }
+  for (double v : p) total += v;
+  std::vector<float> out(n);
+  for (int i = 0; i < n; ++i) out[i] = static_cast<float>(p[i] / total);
+  return out;
+}
+
+hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+#define NUTLS_PCM_DECODE(Q, UP) \
+  return s16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s) \
+             : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s)
+  switch (rate_hz) {
+    case 8000: NUTLS_PCM_DECODE(2, true);
+    case 16000: NUTLS_PCM_DECODE(1, false);
+    case 32000: NUTLS_PCM_DECODE(2, false);
+    case 48000: NUTLS_PCM_DECODE(3, false);
+    default: return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_DECODE
+}
+
+hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+#define NUTLS_PCM_ENCODE(Q, UP) \
+  return s16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s) \
+             : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s)
+  switch (rate_hz) {
+    case 8000: NUTLS_PCM_ENCODE(2, false);
+    case 16000: NUTLS_PCM_ENCODE(1, false);
+    case 32000: NUTLS_PCM_ENCODE(2, true);
+    case 48000: NUTLS_PCM_ENCODE(3, true);
+    default: return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_ENCODE
+}
+
+}  // namespace nutls

@@ -51,6 +51,10 @@ ABI_SYMBOLS = (
     "nutls_process_block_ragged", "nutls_process_block_ragged_host", "nutls_enhance_block_ragged", "nutls_enhance_block_ragged_host",
     "nutls_stft_block_ragged", "nutls_istft_block_ragged",
     "nutls_launch_conv_shape", "nutls_conv_dispatch",
+    "nutls_set_pcm_format", "nutls_pcm_hop_samples", "nutls_pcm_delay_samples", "nutls_pcm_filter_taps", "nutls_pcm_filter",
+    "nutls_enhance_hop_pcm", "nutls_enhance_hop_pcm_active", "nutls_enhance_hop_pcm_host", "nutls_enhance_hop_pcm_host_active",
+    "nutls_pcm_decode_hop", "nutls_pcm_encode_hop",
+    "nutls_enhance_block_pcm", "nutls_enhance_block_pcm_host", "nutls_pcm_decode_block", "nutls_pcm_encode_block",
 )
 
 
@@ -132,6 +136,23 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         ip, lp = c.POINTER(c.c_int), c.POINTER(c.c_longlong)
         lib.nutls_launch_conv_shape.argtypes = [c.c_void_p, c.c_int, ip, ip]
         lib.nutls_conv_dispatch.argtypes = [c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_longlong, ip, ip, ip, lp, lp]
+    if not dev_lib or hasattr(lib, "nutls_set_pcm_format"):
+        vp = c.c_void_p
+        lib.nutls_set_pcm_format.argtypes = [vp, c.c_int, c.c_int]
+        lib.nutls_pcm_hop_samples.argtypes = [vp]
+        lib.nutls_pcm_delay_samples.argtypes = [vp]
+        lib.nutls_pcm_filter_taps.argtypes = [c.c_int]
+        lib.nutls_pcm_filter.argtypes = [c.c_int, fp, c.c_int]
+        lib.nutls_enhance_hop_pcm.argtypes = [vp, vp, vp, c.c_int, vp]
+        lib.nutls_enhance_hop_pcm_active.argtypes = [vp, vp, vp, vp, c.c_int, vp]
+        lib.nutls_enhance_hop_pcm_host.argtypes = [vp, vp, vp, c.c_int]
+        lib.nutls_enhance_hop_pcm_host_active.argtypes = [vp, vp, vp, vp, c.c_int]
+        lib.nutls_pcm_decode_hop.argtypes = [vp, vp, vp, vp, vp]
+        lib.nutls_pcm_encode_hop.argtypes = [vp, vp, vp, vp, vp]
+        lib.nutls_enhance_block_pcm.argtypes = [vp, vp, vp, c.c_int, c.c_int, vp]
+        lib.nutls_enhance_block_pcm_host.argtypes = [vp, vp, vp, c.c_int, c.c_int]
+        lib.nutls_pcm_decode_block.argtypes = [vp, vp, vp, c.c_int, vp]
+        lib.nutls_pcm_encode_block.argtypes = [vp, vp, vp, c.c_int, vp]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -194,6 +215,59 @@ def host_alloc(shape, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
     return arr
 
 
+def pcm_filter(rate: int, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
+    """The fp32 prototype filter the PCM gateway's kernels use for ``rate`` (8000, 32000, 48000: ``2 * 24 * q + 1`` taps; 16000: the single
+    tap 1.0) -- ``nutls_pcm_filter``.  Host only: needs no GPU."""
+    lib = lib or load_library()
+    n = lib.nutls_pcm_filter_taps(int(rate))
+    if n < 0:
+        raise ValueError("rate must be 8000, 16000, 32000 or 48000, got %r" % (rate,))
+    taps = np.empty(n, np.float32)
+    _check(lib, lib.nutls_pcm_filter(int(rate), _fptr(taps), n))
+    return taps
+
+
+class _PcmFormat:
+    """The callers' sample format of a handle (``nutls_set_pcm_format``): shared by :class:`NutlsEngine` and :class:`NutlsOffline`."""
+
+    _PCM_FORMATS = {"float32": 0, "int16": 1}
+    pcm_rate, pcm_dtype = 16000, "float32"
+
+    def set_pcm_format(self, rate: int = 16000, dtype="float32") -> None:
+        """What the ``_pcm`` methods take and return from now on: ``rate`` 8000, 16000, 32000 or 48000, ``dtype`` "float32" or "int16"
+        (32768 = 1.0).  May be called between any two hops; every stream's resampler history restarts from zeros.  The other methods keep
+        taking float32 at 16 kHz."""
+        name = np.dtype(dtype).name
+        if name not in self._PCM_FORMATS:
+            raise ValueError("dtype must be float32 or int16, got %s" % name)
+        _check(self._lib, self._lib.nutls_set_pcm_format(self._h, int(rate), self._PCM_FORMATS[name]))
+        self.pcm_rate, self.pcm_dtype = int(rate), name
+
+    @property
+    def pcm_hop_samples(self) -> int:
+        """Samples of one 16 ms hop at the callers' rate: 128, 256, 512 or 768."""
+        return int(self._lib.nutls_pcm_hop_samples(self._h))
+
+    @property
+    def pcm_delay_samples(self) -> int:
+        """Delay of the two rate conversions together, in samples at the callers' rate (0 at 16 kHz); the one-hop lag of ``enhance_hop``
+        comes on top."""
+        return int(self._lib.nutls_pcm_delay_samples(self._h))
+
+    def _pcm_tensor(self, x, rows: int, cols: int, name: str, dtype=None):
+        """A contiguous CUDA tensor ``[rows, cols]`` of the handle's sample type (or ``dtype``)."""
+        import torch
+        want = dtype or getattr(torch, self.pcm_dtype)
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == want and x.is_contiguous() and tuple(x.shape) == (rows, cols)):
+            raise ValueError("%s must be a contiguous %s CUDA tensor [%d,%d]" % (name, str(want).replace("torch.", ""), rows, cols))
+        return x
+
+    def _pcm_array(self, x, rows: int, cols: int, name: str):
+        if not (isinstance(x, np.ndarray) and x.dtype.name == self.pcm_dtype and x.flags.c_contiguous and x.shape == (rows, cols)):
+            raise ValueError("%s must be a contiguous %s numpy array [%d,%d]" % (name, self.pcm_dtype, rows, cols))
+        return x
+
+
 # the kinds of the per-layer conv kernels, in the library's order (csrc/nutls_internal.hpp ConvKind)
 CONV_KINDS = ("el_c32", "el_c64", "el_c128", "dl_n64", "dl_n128", "in_c64", "in_c128", "down", "up_even", "up_odd")
 
@@ -224,7 +298,7 @@ def conv_launches(lib, handle) -> List[Tuple[str, str, int]]:
     return res
 
 
-class NutlsEngine:
+class NutlsEngine(_PcmFormat):
     """B streams, device-resident state.  ``step`` takes/returns ``[B,256]`` magnitudes."""
 
     MODES = {"launches": 0, "graph": 1, "fused": 3}
@@ -438,6 +512,55 @@ class NutlsEngine:
         stream = torch.cuda.current_stream(out.device).cuda_stream
         _check(self._lib, self._lib.nutls_istft_hop(self._h, out.data_ptr(), self._DC[dc_mode], stream))
         return out
+
+    # -- PCM gateway: the callers' sample rate and type, converted on the device (csrc/pcm.hip) ---------------------------------
+    def enhance_hop_pcm(self, pcm, dc_mode: str = "edge", out=None, active=None):
+        """``enhance_hop`` in the format of ``set_pcm_format``: ``pcm [B, pcm_hop_samples]`` of the handle's sample type, a CUDA tensor
+        (``nutls_enhance_hop_pcm``, asynchronous on the current torch stream) or a numpy array (``nutls_enhance_hop_pcm_host``, synchronous)
+        -> the enhanced hop in the same format, ``pcm_delay_samples`` plus one hop late.  ``active``: as in ``enhance_hop`` -- a held
+        stream's resampler history stays as it is too.  At 16000 / float32 this IS ``enhance_hop``."""
+        if dc_mode not in self._DC:
+            raise ValueError("dc_mode must be 'edge' or 'zero'")
+        S = self.pcm_hop_samples
+        if isinstance(pcm, np.ndarray):
+            x = self._pcm_array(pcm, self.batch, S, "pcm")
+            o = np.empty_like(x) if out is None else self._pcm_array(out, self.batch, S, "out")
+            if active is not None:
+                a = self._host_mask(active)
+                _check(self._lib, self._lib.nutls_enhance_hop_pcm_host_active(self._h, x.ctypes.data, o.ctypes.data, a.ctypes.data, self._DC[dc_mode]))
+            else:
+                _check(self._lib, self._lib.nutls_enhance_hop_pcm_host(self._h, x.ctypes.data, o.ctypes.data, self._DC[dc_mode]))
+            return o
+        import torch
+        x = self._pcm_tensor(pcm, self.batch, S, "pcm")
+        o = torch.empty_like(x) if out is None else self._pcm_tensor(out, self.batch, S, "out")
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if active is not None:
+            _check(self._lib, self._lib.nutls_enhance_hop_pcm_active(self._h, x.data_ptr(), o.data_ptr(), self._device_mask(active, x),
+                                                                     self._DC[dc_mode], stream))
+        else:
+            _check(self._lib, self._lib.nutls_enhance_hop_pcm(self._h, x.data_ptr(), o.data_ptr(), self._DC[dc_mode], stream))
+        return o
+
+    def pcm_decode_hop(self, pcm, out=None, active=None):
+        """The decode half on its own: CUDA tensor ``[B, pcm_hop_samples]`` of the handle's sample type -> ``[B,256]`` float32 at 16 kHz
+        (what ``enhance_hop`` takes).  ``active``: device mask; a held row of the result is zeros."""
+        import torch
+        x = self._pcm_tensor(pcm, self.batch, self.pcm_hop_samples, "pcm")
+        o = torch.empty((self.batch, 256), dtype=torch.float32, device=x.device) if out is None else self._pcm_tensor(out, self.batch, 256, "out", torch.float32)
+        a = None if active is None else self._device_mask(active, x)
+        _check(self._lib, self._lib.nutls_pcm_decode_hop(self._h, x.data_ptr(), o.data_ptr(), a, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
+
+    def pcm_encode_hop(self, hop, out=None, active=None):
+        """The encode half on its own: ``[B,256]`` float32 CUDA tensor at 16 kHz -> ``[B, pcm_hop_samples]`` of the handle's sample type."""
+        import torch
+        x = self._pcm_tensor(hop, self.batch, 256, "hop", torch.float32)
+        S = self.pcm_hop_samples
+        o = torch.empty((self.batch, S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None else self._pcm_tensor(out, self.batch, S, "out")
+        a = None if active is None else self._device_mask(active, x)
+        _check(self._lib, self._lib.nutls_pcm_encode_hop(self._h, x.data_ptr(), o.data_ptr(), a, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
 
     def step_resident(self, stream: int = 0):
         """Step on the library-owned I/O buffers (``io_in_ptr`` / ``io_out_ptr``): no copies."""
@@ -661,7 +784,7 @@ def plan_ragged_blocks(lengths_in_hops, utterances: int, max_frames: int):
         blocks.append(block)
 
 
-class NutlsOffline:
+class NutlsOffline(_PcmFormat):
     """Offline / block mode: ``utterances`` independent utterances, up to ``max_frames`` consecutive frames of each
     per call -- every conv-like layer runs once per block over all frames of all utterances (the frame index takes the place of
     the stream index), only the LSTM recurrences are scanned (side by side for the utterances).  Same function as a streaming
@@ -878,6 +1001,93 @@ class NutlsOffline:
             blk = np.ascontiguousarray(x[:, a * 256:b * 256])
             out[:, a * 256:b * 256] = self.enhance_block_host(blk, None, dc_mode)
         out = out[:, 256:]
+        return out if batched else out[0]
+
+    # -- PCM gateway: blocks in the callers' sample rate and type (csrc/pcm.hip) ---------------------------------------------------
+    def _pcm_block_hops(self, cols: int, unit: int, name: str) -> int:
+        if cols % unit or not 1 <= cols // unit <= self.max_frames:
+            raise ValueError("%s must be [%d, n_hops*%d] with 1 <= n_hops <= %d" % (name, self.utterances, unit, self.max_frames))
+        return cols // unit
+
+    def enhance_block_pcm_device(self, pcm, out=None, dc_mode: str = "edge"):
+        """``enhance_block_device`` in the format of ``set_pcm_format``: ``pcm [utterances, n_hops * pcm_hop_samples]`` CUDA tensor of the
+        handle's sample type -> the enhanced block in the same format (``nutls_enhance_block_pcm``), ``pcm_delay_samples`` plus one hop late;
+        the resampler histories carry from block to block."""
+        import torch
+        dc = self._dc(dc_mode)
+        S = self.pcm_hop_samples
+        n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
+        x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
+        o = torch.empty_like(x) if out is None else self._pcm_tensor(out, self.utterances, n * S, "out")
+        _check(self._lib, self._lib.nutls_enhance_block_pcm(self._h, x.data_ptr(), o.data_ptr(), n, dc, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
+
+    def enhance_block_pcm_host(self, pcm: np.ndarray, out: Optional[np.ndarray] = None, dc_mode: str = "edge") -> np.ndarray:
+        """The same on host arrays (``nutls_enhance_block_pcm_host``; synchronous)."""
+        dc = self._dc(dc_mode)
+        S = self.pcm_hop_samples
+        n = self._pcm_block_hops(pcm.shape[-1] if isinstance(pcm, np.ndarray) and pcm.ndim == 2 else -1, S, "pcm")
+        x = self._pcm_array(pcm, self.utterances, n * S, "pcm")
+        o = np.empty_like(x) if out is None else self._pcm_array(out, self.utterances, n * S, "out")
+        _check(self._lib, self._lib.nutls_enhance_block_pcm_host(self._h, x.ctypes.data, o.ctypes.data, n, dc))
+        return o
+
+    def pcm_decode_block_device(self, pcm, out=None):
+        """The decode half on its own: ``[utterances, n_hops * pcm_hop_samples]`` of the handle's sample type -> ``[utterances, n_hops*256]``
+        float32 at 16 kHz (what ``enhance_block_device`` takes)."""
+        import torch
+        S = self.pcm_hop_samples
+        n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
+        x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
+        o = (torch.empty((self.utterances, n * 256), dtype=torch.float32, device=x.device) if out is None
+             else self._pcm_tensor(out, self.utterances, n * 256, "out", torch.float32))
+        _check(self._lib, self._lib.nutls_pcm_decode_block(self._h, x.data_ptr(), o.data_ptr(), n, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
+
+    def pcm_encode_block_device(self, wave, out=None):
+        """The encode half on its own: ``[utterances, n_hops*256]`` float32 at 16 kHz -> the handle's format."""
+        import torch
+        S = self.pcm_hop_samples
+        n = self._pcm_block_hops(int(wave.shape[-1]) if hasattr(wave, "shape") and len(wave.shape) == 2 else -1, 256, "wave")
+        x = self._pcm_tensor(wave, self.utterances, n * 256, "wave", torch.float32)
+        o = (torch.empty((self.utterances, n * S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None
+             else self._pcm_tensor(out, self.utterances, n * S, "out"))
+        _check(self._lib, self._lib.nutls_pcm_encode_block(self._h, x.data_ptr(), o.data_ptr(), n, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
+
+    def _wave_through_blocks(self, x: np.ndarray, lag: int, block) -> np.ndarray:
+        """``x [utterances, N]`` of the handle's sample type, padded with zeros to whole hops that cover ``N + lag`` samples, through
+        ``block`` (array ``[utterances, n_hops * pcm_hop_samples]`` -> array of the same shape, n_hops <= max_frames) in blocks of
+        ``max_frames`` hops; the first ``lag`` samples of the result are dropped, so that sample i of what is returned belongs to ``x[:, i]``."""
+        S = self.pcm_hop_samples
+        n = x.shape[1]
+        hops = max(1, -(-(n + lag) // S))
+        padded = np.zeros((self.utterances, hops * S), x.dtype)
+        padded[:, :n] = x
+        out = np.empty_like(padded)
+        for a in range(0, hops, self.max_frames):
+            b = min(hops, a + self.max_frames)
+            out[:, a * S:b * S] = block(np.ascontiguousarray(padded[:, a * S:b * S]))
+        return out[:, lag:lag + n]
+
+    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge") -> np.ndarray:
+        """A whole recording in its own format: ``wave [N]`` (one utterance) or ``[utterances, N]``, int16 or float32 numpy array of any
+        length at ``rate`` (8000, 16000, 32000, 48000) -> the enhanced recording of the same shape and dtype, ALIGNED with the input:
+        sample i of the result belongs to ``wave[i]`` (the input is padded with zeros to whole hops plus the total lag, one hop plus
+        ``pcm_delay_samples``, and that lag is dropped from the front).  Sets the handle's format (``set_pcm_format``: the rate conversion
+        starts from a zero history); the model state carries on from earlier calls until :meth:`reset`."""
+        self._dc(dc_mode)
+        x = np.asarray(wave)
+        if x.dtype.name not in self._PCM_FORMATS:
+            raise ValueError("wave must be int16 or float32, got %s" % x.dtype.name)
+        batched = x.ndim == 2
+        if x.ndim == 1 and self.utterances == 1:
+            x = x[None]
+        if x.ndim != 2 or x.shape[0] != self.utterances:
+            raise ValueError("wave must be [%sN], got %s" % ("%d," % self.utterances if self.utterances > 1 else "", np.shape(wave)))
+        self.set_pcm_format(rate, x.dtype)
+        lag = self.pcm_hop_samples + self.pcm_delay_samples
+        out = self._wave_through_blocks(x, lag, lambda blk: self.enhance_block_pcm_host(blk, None, dc_mode))
         return out if batched else out[0]
 
     # -- ragged blocks: per-utterance counts (nutls_process_block_ragged_host / nutls_enhance_block_ragged_host) ---------------------
