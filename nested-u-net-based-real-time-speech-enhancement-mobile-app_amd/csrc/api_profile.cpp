@@ -223,6 +223,7 @@ int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, i
   HIP_TRY(hipEventCreate(&ev[0]));
   HIP_TRY(hipEventCreate(&ev[1]));
   int rc = NUTLS_OK;
+  const int stop_before = e->fz_stop_at;      // (NUTLS_FUSED_STOP_TWIN handles keep running the twin afterwards)
   auto run = [&](int stop, int count) {
     e->fz_stop_at = stop;
     for (int i = 0; i < count && !rc; ++i) {
@@ -244,7 +245,7 @@ int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, i
     }
     cum_us[stop] = best;
   }
-  e->fz_stop_at = -1;
+  e->fz_stop_at = stop_before;
   (void)hipEventDestroy(ev[0]);
   (void)hipEventDestroy(ev[1]);
   if (rc) return rc;

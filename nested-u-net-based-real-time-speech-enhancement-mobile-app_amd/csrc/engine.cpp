@@ -777,6 +777,16 @@ static int fused_setup(Engine* e, const WeightMap& wm) {
   }
   if (const char* ev = getenv("NUTLS_EAGER_STATES")) e->eager_states = atoi(ev) != 0;      // (developer knob: every launch writes every state)
   if (const char* ev = getenv("NUTLS_FUSED_SKEW")) e->fz_skew = atoi(ev);
+  // (developer knob: every step of the handle runs the stop twin to the end -- op index num_ops is never reached -- so that a test can hold
+  //  its instruction stream to the production kernel's results; one-stream plan of the LSTM variant, the only kernel that has a twin)
+  if (const char* ev = getenv("NUTLS_FUSED_STOP_TWIN")) {
+    if (atoi(ev) != 0) {
+      if (e->variant != NUTLS_VARIANT_LSTM || plan.streams != 1)
+        return fail(NUTLS_ERR_ARG, "NUTLS_FUSED_STOP_TWIN: the stop twin exists for the one-stream plan of the LSTM variant only");
+      HIP_TRY(fused_step_stop_set_attributes());
+      e->fz_stop_at = plan.num_ops;
+    }
+  }
   return NUTLS_OK;
 }
 

@@ -96,6 +96,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef const char __attribute__((address_space(1))) * gcb_t;
 typedef char __attribute__((address_space(1))) * gb_t;
@@ -156,6 +157,43 @@ __device__ __forceinline__ f32x4 ldb(gcb_t base, unsigned boff) { return *(gc4_t
 __device__ __forceinline__ float ldb1(gcb_t base, unsigned boff) { return *(gcf_t)(base + static_cast<unsigned long long>(boff)); }
 __device__ __forceinline__ void stb(gcb_t base, unsigned boff, f32x4 v) { *(g4_t)((gb_t)(unsigned long long)base + static_cast<unsigned long long>(boff)) = v; }
 __device__ __forceinline__ void stb1(gcb_t base, unsigned boff, float v) { *(gf_t)((gb_t)(unsigned long long)base + static_cast<unsigned long long>(boff)) = v; }
+// Address of a load whose base and constant (or wave-uniform) byte offset are the same for every lane: base + offset go into an SGPR pair the
+// optimiser cannot take apart again, the lane's part stays a 32-bit VGPR offset and at most 4095 bytes ride in the instruction's immediate
+// (global_load v, v_off, s[base:base+1] offset:imm).  Left to itself the compiler adds the lane offset to the base FIRST -- a 64-bit VGPR
+// address -- and the constant after it, with two more VALU adds (and a hazard nop) whenever it does not fit the immediate: 1 500 VALU
+// instructions of the one-stream kernel built addresses that way, in front of the first B read of every op.
+// (One-stream plans.  The packed kernels sit at the register file's limit -- 255 / 256 VGPRs, the four-stream one spilling -- and were tuned with the
+//  forms the compiler chooses by itself; pinning them moved their allocation (one and five more spilled registers): there FZ_PINNED_FORMS is 0 and
+//  ubase is plain pointer arithmetic, as are the other forms this switch guards.)
+constexpr bool FZ_PINNED_FORMS = kStreams == 1;
+__device__ __forceinline__ gcb_t ubase(gcb_t base, unsigned uoff) {
+  if constexpr (FZ_PINNED_FORMS) { if (!__builtin_constant_p(uoff)) asm("" : "+s"(uoff)); }      // (a run-time offset as ONE scalar: not its constant part in a second 64-bit add)
+  gcb_t p = base + static_cast<unsigned long long>(uoff);
+  if constexpr (FZ_PINNED_FORMS) asm("" : "+s"(p));
+  return p;
+}
+// (uoff: uniform byte offset, usually a constant; voff: the lane's byte offset)
+// (packed builds: the one 32-bit offset `uoff + voff` they were tuned with -- a scalar base per load costs the four-stream kernel 20 000 scalar instructions)
+__device__ __forceinline__ f32x4 ldu(gcb_t base, unsigned uoff, unsigned voff) {
+  if constexpr (!FZ_PINNED_FORMS) return *(gc4_t)(base + static_cast<unsigned long long>(uoff + voff));
+  else return *(gc4_t)(ubase(base, uoff & ~0xfffu) + static_cast<unsigned long long>(voff) + static_cast<unsigned long long>(uoff & 0xfffu));
+}
+__device__ __forceinline__ void stu1(gcb_t base, unsigned uoff, unsigned voff, float v) {
+  if constexpr (!FZ_PINNED_FORMS) *(gf_t)((gb_t)(unsigned long long)base + static_cast<unsigned long long>(uoff + voff)) = v;
+  else *(gf_t)((gb_t)(unsigned long long)ubase(base, uoff & ~0xfffu) + static_cast<unsigned long long>(voff) + static_cast<unsigned long long>(uoff & 0xfffu)) = v;
+}
+__device__ __forceinline__ float ldu1(gcb_t base, unsigned uoff, unsigned voff) {
+  if constexpr (!FZ_PINNED_FORMS) return *(gcf_t)(base + static_cast<unsigned long long>(uoff + voff));
+  else return *(gcf_t)(ubase(base, uoff & ~0xfffu) + static_cast<unsigned long long>(voff) + static_cast<unsigned long long>(uoff & 0xfffu));
+}
+// Weight fragments of a wave task: super-fragment sf = 1 KB (a dwordx4 per lane) at wtask + 1024 sf; wtask = ubase(blob, offset of the task)
+template <int SF>
+__device__ __forceinline__ f32x4 ldw(gcb_t wtask, unsigned lane16) {
+  if constexpr (FZ_PINNED_FORMS) asm("" : "+v"(lane16));      // (not the 64-bit copy of the same offset another address of the op may have made: base + that is a VGPR address again)
+  if constexpr (!FZ_PINNED_FORMS) return *(gc4_t)(wtask + static_cast<unsigned long long>(SF * 1024) + static_cast<unsigned long long>(lane16));
+  else if constexpr (SF < 4) return *(gc4_t)(wtask + static_cast<unsigned long long>(lane16) + static_cast<unsigned long long>(SF * 1024));
+  else return *(gc4_t)(ubase(wtask, (SF / 4) * 4096u) + static_cast<unsigned long long>(lane16) + static_cast<unsigned long long>((SF % 4) * 1024));
+}
 // Cache policy (round 6; profiles/r06_dev_log.txt "nt"): every ACTIVATION is read exactly once per launch, by the one workgroup that owns the stream -- the
 // previous frame's state rows and carried sums (written a whole launch ago), this frame's skip / residual / up-sampling rows -- while the WEIGHTS are read by
 // all 32 workgroups of an XCD within microseconds of each other and again next launch.  With plain loads the 2 MB of activations a stream pulls through the
@@ -170,11 +208,29 @@ __device__ __forceinline__ void st_next1(gcb_t base, unsigned boff, float v) { _
 // a state store: non-temporal when nothing in this launch reads the rows again (OpD::nt0 / nt1)
 template <bool NT> __device__ __forceinline__ void st_state(gcb_t base, unsigned boff, f32x4 v) { if constexpr (NT) st_next(base, boff, v); else stb(base, boff, v); }
 template <bool NT> __device__ __forceinline__ void st_state1(gcb_t base, unsigned boff, float v) { if constexpr (NT) st_next1(base, boff, v); else stb1(base, boff, v); }
+// the read-once loads in that form (ucst: constant byte offset; urt: a wave-uniform one known at run time only -- a packed plan's stream slot -- that goes
+// into the scalar base whole)
+__device__ __forceinline__ f32x4 ldu_once(gcb_t base, unsigned ucst, unsigned urt, unsigned voff) {
+  if constexpr (!FZ_PINNED_FORMS) return __builtin_nontemporal_load((gc4_t)(base + static_cast<unsigned long long>(ucst + voff + urt)));
+  else return __builtin_nontemporal_load((gc4_t)(ubase(base, (ucst & ~0xfffu) + urt) + static_cast<unsigned long long>(voff) + static_cast<unsigned long long>(ucst & 0xfffu)));
+}
+__device__ __forceinline__ float ldu_once1(gcb_t base, unsigned ucst, unsigned urt, unsigned voff) {
+  if constexpr (!FZ_PINNED_FORMS) return __builtin_nontemporal_load((gcf_t)(base + static_cast<unsigned long long>(ucst + voff + urt)));
+  else return __builtin_nontemporal_load((gcf_t)(ubase(base, (ucst & ~0xfffu) + urt) + static_cast<unsigned long long>(voff) + static_cast<unsigned long long>(ucst & 0xfffu)));
+}
 extern __shared__ __attribute__((aligned(16))) float lds[];
-__device__ __forceinline__ f32x4& lds4(int boff) { return *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds) + boff); }
-__device__ __forceinline__ float& lds1(int boff) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + boff); }
-__device__ __forceinline__ u32x2& lds2u(int boff) { return *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(lds) + boff); }
-__device__ __forceinline__ unsigned short& lds_h(int boff) { return *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(lds) + boff); }
+// The accessors address LDS by NUMBER, not through `lds`: the kernels have no static LDS, so the dynamic block starts at byte 0 (FZ_ATTR refuses a
+// build whose kernel has static LDS).  The compiler learns the symbol's address only after instruction selection: through it every LDS address
+// carried an unfolded `+ 0` -- six to eight VALU / SALU instructions per small op that compute nothing.
+typedef char __attribute__((address_space(3))) * lb_t;
+__device__ __forceinline__ f32x4& lds4(int boff) { if constexpr (FZ_PINNED_FORMS) return *(f32x4*)(lb_t)boff; else return *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds) + boff); }
+__device__ __forceinline__ float& lds1(int boff) { if constexpr (FZ_PINNED_FORMS) return *(float*)(lb_t)boff; else return *reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + boff); }
+__device__ __forceinline__ u32x2& lds2u(int boff) { if constexpr (FZ_PINNED_FORMS) return *(u32x2*)(lb_t)boff; else return *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(lds) + boff); }
+__device__ __forceinline__ unsigned short& lds_h(int boff) { if constexpr (FZ_PINNED_FORMS) return *(unsigned short*)(lb_t)boff; else return *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(lds) + boff); }
+// ... except the parameter block of the 32x32-tile epilogue, which keeps the symbol (lds4s / lds1s): addressed by number, the compiler holds one
+// address register per parameter row across that epilogue, and the kernel's fullest point (the msfe6 decoder convs) goes from 215 to 217 VGPRs.
+__device__ __forceinline__ f32x4& lds4s(int boff) { return *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(lds) + boff); }
+__device__ __forceinline__ float& lds1s(int boff) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + boff); }
 // workgroup barrier that orders LDS traffic only (global loads / stores stay in flight across it)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -441,7 +497,17 @@ __device__ __forceinline__ void stage_load(const Ctx& cx, int tid, f32x4 (&r)[NR
           const int gi = NG > 1 ? q >> clog2(per) : 0;                     // stream of the item (packed plans)
           if constexpr (NG > 1) q &= per - 1;
           const int row = q >> cs, c4 = q & (p.c4s - 1);
-          r[base + i] = ld_once(src, static_cast<unsigned>(p.off * 4 + row * (p.ld * 4) + c4 * 16) + gofs(cx, PG0 + gi));
+          // (the part's offset and a uniform stream slot in the scalar base; a packed block's per-item slot with the lane's offset)
+          if constexpr (NG > 1) {
+            r[base + i] = ldu_once(src, static_cast<unsigned>(p.off * 4), 0u, static_cast<unsigned>(row * (p.ld * 4) + c4 * 16) + gofs(cx, PG0 + gi));
+          } else if constexpr ((i + 1) * NTHR > items || NTHR % p.c4s != 0) {
+            r[base + i] = ldu_once(src, static_cast<unsigned>(p.off * 4), gofs(cx, PG0), static_cast<unsigned>(row * (p.ld * 4) + c4 * 16));
+          } else {
+            // (item slot + NTHR i: the same channel quad, NTHR i / c4s rows further -- a constant, which belongs to the base as well: as part of the
+            //  lane's offset it is again "the first item's address + a constant", in 64-bit vector arithmetic)
+            const int row0 = slot >> cs, c40 = slot & (p.c4s - 1);
+            r[base + i] = ldu_once(src, static_cast<unsigned>(p.off * 4 + (NTHR * i / p.c4s) * (p.ld * 4)), gofs(cx, PG0), static_cast<unsigned>(row0 * (p.ld * 4) + c40 * 16));
+          }
         });
       }
     });
@@ -486,9 +552,18 @@ __device__ __forceinline__ void zero_halos(int tid) {
         constexpr int K = decltype(kk)::value + 1;
         delta = tid >= zero_start(g, K) ? g.zero[K].lds_b - zero_start(g, K) * 16 : delta;
       });
-      float zf = 0.f;
-      asm volatile("" : "+v"(zf));
-      const f32x4 z = {zf, zf, zf, zf};
+      // (the zeros as two 64-bit halves: v_mov_b64 twice, not one zero and three copies of it)
+      f32x4 z;
+      if constexpr (FZ_PINNED_FORMS) {
+        unsigned long long z0 = 0ull, z1 = 0ull;
+        asm volatile("" : "+v"(z0), "+v"(z1));
+        const u64x2 zq = {z0, z1};
+        z = __builtin_bit_cast(f32x4, zq);
+      } else {
+        float zf = 0.f;
+        asm volatile("" : "+v"(zf));
+        z = f32x4{zf, zf, zf, zf};
+      }
       if (static_cast<unsigned>(tid - zero_first(g)) < static_cast<unsigned>(zero_total(g))) {
         lds4(delta + tid * 16) = z;
         sfor<kOps[J].gs - 1>([&](auto gg) { lds4(delta + tid * 16 + (decltype(gg)::value + 1) * g.gstride_b) = z; });      // (packed plans: every stream's sub-image)
@@ -533,10 +608,18 @@ __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8 
 }
 // The carried weights become visible to the optimiser only here: without this it hoists the byte extraction up to the
 // loads in the previous op -- and waits for them there, which turns the prefetch into a synchronous load.
-template <int N>
+// (ONE statement for up to 6 registers, the LAST ones of the array -- the youngest loads -- first: the wait for a pinned load sits in front of its
+//  statement, and one statement per register in load order was a `vmcnt(a)` / `vmcnt(a - 1)` pair wherever two of them had landed in order)
+template <int N, int TOP = N>
 __device__ __forceinline__ void pin_regs(f32x4 (&r)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r[i]));
+  constexpr int n = FZ_PINNED_FORMS ? cmin(6, TOP) : 1, AT = TOP - n;      // (an inline asm statement takes at most 30 operands; "+v" counts twice)
+  if constexpr (n == 1) asm volatile("" : "+v"(r[AT]));
+  else if constexpr (n == 2) asm volatile("" : "+v"(r[AT]), "+v"(r[AT + 1]));
+  else if constexpr (n == 3) asm volatile("" : "+v"(r[AT]), "+v"(r[AT + 1]), "+v"(r[AT + 2]));
+  else if constexpr (n == 4) asm volatile("" : "+v"(r[AT]), "+v"(r[AT + 1]), "+v"(r[AT + 2]), "+v"(r[AT + 3]));
+  else if constexpr (n == 5) asm volatile("" : "+v"(r[AT]), "+v"(r[AT + 1]), "+v"(r[AT + 2]), "+v"(r[AT + 3]), "+v"(r[AT + 4]));
+  else if constexpr (n == 6) asm volatile("" : "+v"(r[AT]), "+v"(r[AT + 1]), "+v"(r[AT + 2]), "+v"(r[AT + 3]), "+v"(r[AT + 4]), "+v"(r[AT + 5]));
+  if constexpr (AT > 0) pin_regs<N, AT>(r);
 }
 
 // "Defined, contents unknown" without an instruction: registers only one wave-branch loads (gates_load) get an opaque definition on the other path,
@@ -583,16 +666,16 @@ __device__ __forceinline__ void prefetch_w(const Ctx& cx, int tid, f32x4 (&w)[NW
       const Task t = conv_task<I>(wave);
       // wave-uniform base (SGPR pair) + lane offset (VGPR) + immediate: no 64-bit vector address arithmetic
       // (a wave without a task fetches the fragments of task wave mod ntask and never uses them)
-      const gcb_t wbase = cx.wb + static_cast<unsigned long long>(static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
+      const gcb_t wbase = ubase(cx.wb, static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
       sfor<carry_w(I)>([&](auto ff) {
         constexpr int sf = decltype(ff)::value;
-        w[sf] = ldb(wbase + static_cast<unsigned long long>(sf * 1024), static_cast<unsigned>(lane * 16));
+        w[sf] = ldw<sf>(wbase, static_cast<unsigned>(lane * 16));
       });
       if constexpr (prm_dword(d)) {
-        prm[0] = ldb1(cx.wb + static_cast<unsigned long long>(d.p_off * 4), static_cast<unsigned>((tid < nparams(d) ? tid : nparams(d) - 1) * 4));
+        prm[0] = ldu1(cx.wb, static_cast<unsigned>(d.p_off * 4), static_cast<unsigned>((tid < nparams(d) ? tid : nparams(d) - 1) * 4));
       } else {
         constexpr int NP4 = (nparams(d) + 3) / 4;
-        prm = ldb(cx.wb + static_cast<unsigned long long>(d.p_off * 4), static_cast<unsigned>((tid < NP4 ? tid : NP4 - 1) * 16));
+        prm = ldu(cx.wb, static_cast<unsigned>(d.p_off * 4), static_cast<unsigned>((tid < NP4 ? tid : NP4 - 1) * 16));
       }
     } else if constexpr (d.type == T_LSTM) {
       // everything lstm_op needs from memory (slot map there), one op ahead; branch-free (see above): thread (u, sl) loads the NRP int8x4 rows
@@ -605,26 +688,27 @@ __device__ __forceinline__ void prefetch_w(const Ctx& cx, int tid, f32x4 (&w)[NW
       const int hs = sl - 16;
       sfor<NRP / 4>([&](auto jj) {
         constexpr int j = decltype(jj)::value;
-        w[j] = ldb(cx.wb, static_cast<unsigned>((WB + (sl * 21 + u) * NRP + 4 * j) * 4));
+        w[j] = ldu(cx.wb, static_cast<unsigned>((WB + 4 * j) * 4), static_cast<unsigned>((sl * 21 + u) * (NRP * 4)));
       });
       const int h0 = xs ? 0 : 6 * hs;
       sfor<6 * d.gs>([&](auto jj) {
         constexpr int j = decltype(jj)::value % 6, gi = decltype(jj)::value / 6, SH = gi == 0 ? S0 : S0 + 10 + 2 * (gi - 1);
-        w[SH + j / 4][j % 4] = ld_once1(cx.sbp, static_cast<unsigned>((d.h_off + h0 + j) * 4) + gofs(cx, d.g0 + gi));      // (h[21..23]: slot padding, zero)
+        w[SH + j / 4][j % 4] = ldu_once1(cx.sbp, static_cast<unsigned>((d.h_off + j) * 4), gofs(cx, d.g0 + gi), static_cast<unsigned>(h0 * 4));      // (h[21..23]: slot padding, zero)
       });
       // (packed plans: gates and Dense outputs are dealt to threads as (stream, unit) / (stream, output): thread tid owns unit tid % 21 of
       //  stream tid / 21 and output tid % dout -- of stream (tid + 512 pass) / dout)
       const int drow = d.gs > 1 ? (tid & (d.dout - 1)) : (tid < d.dout ? tid : d.dout - 1);
       sfor<DROW / 4>([&](auto jj) {
         constexpr int j = decltype(jj)::value;
-        w[S0 + 2 + j] = ldb(cx.wb, static_cast<unsigned>((WD + drow * DROW + 4 * j) * 4));
+        w[S0 + 2 + j] = ldu(cx.wb, static_cast<unsigned>((WD + 4 * j) * 4), static_cast<unsigned>(drow * (DROW * 4)));
       });
       const int u21 = d.gs > 1 ? (tid < 21 * d.gs ? tid % 21 : 20) : (tid < 21 ? tid : 20);
       const int g21 = d.gs > 1 ? (tid < 21 * d.gs ? tid / 21 : d.gs - 1) : 0;          // the stream slot whose cell state this thread updates
-      w[S0 + 8] = ldb(cx.wb, static_cast<unsigned>((REC + 4 * u21) * 4));
-      w[S0 + 9][0] = ld_once1(cx.sbp, static_cast<unsigned>((d.c_off + u21) * 4) + gofs(cx, d.g0 + g21));
-      w[S0 + 9][1] = ldb1(cx.wb, static_cast<unsigned>((REC + 84) * 4));      // s_x
-      w[S0 + 9][2] = ldb1(cx.wb, static_cast<unsigned>((REC + 85) * 4));      // s_h
+      w[S0 + 8] = ldu(cx.wb, static_cast<unsigned>(REC * 4), static_cast<unsigned>(u21 * 16));
+      if constexpr (d.gs == 1) w[S0 + 9][0] = ldu_once1(cx.sbp, static_cast<unsigned>(d.c_off * 4), gofs(cx, d.g0), static_cast<unsigned>(u21 * 4));
+      else w[S0 + 9][0] = ld_once1(cx.sbp, static_cast<unsigned>((d.c_off + u21) * 4) + gofs(cx, d.g0 + g21));
+      w[S0 + 9][1] = ldu1(cx.wb, static_cast<unsigned>((REC + 84) * 4), 0u);      // s_x
+      w[S0 + 9][2] = ldu1(cx.wb, static_cast<unsigned>((REC + 85) * 4), 0u);      // s_h
 #if FZ_BASE
     } else if constexpr (d.type == T_DDB) {
       ddbz_prefetch<THREADS, d.x_cols / 2, d.din / d.x_cols>(ddbz_load_rec(cx.ddb + d.bidx), cx.stream, cx.step, tid, w);
@@ -636,11 +720,13 @@ __device__ __forceinline__ void prefetch_w(const Ctx& cx, int tid, f32x4 (&w)[NW
         constexpr int i = decltype(ii)::value % NI, gi = decltype(ii)::value / NI;
         int f = rg + 32 * i;
         if (f > d.F - 1) f = d.F - 1;
-        w[gi * NI + i] = ld_once(cx.sbc, static_cast<unsigned>((d.e0_off + f * d.e0_ld + 4 * c4) * 4) + gofs(cx, d.g0 + gi));
+        // (a pass none of whose rows is clamped: its 32 i rows are a constant and go into the base)
+        if constexpr (32 * i + 31 <= d.F - 1) w[gi * NI + i] = ldu_once(cx.sbc, static_cast<unsigned>((d.e0_off + 32 * i * d.e0_ld) * 4), gofs(cx, d.g0 + gi), static_cast<unsigned>((rg * d.e0_ld + 4 * c4) * 4));
+        else w[gi * NI + i] = ldu_once(cx.sbc, static_cast<unsigned>(d.e0_off * 4), gofs(cx, d.g0 + gi), static_cast<unsigned>((f * d.e0_ld + 4 * c4) * 4));
       });
       if constexpr (d.last) {
-        w[NI * d.gs] = ldb(cx.wb, static_cast<unsigned>((d.cw_off + 4256 + 4 * c4) * 4));                     // output conv weights
-        w[NI * d.gs + 1][0] = ldb1(cx.wb, static_cast<unsigned>((d.cw_off + 4320) * 4));
+        w[NI * d.gs] = ldu(cx.wb, static_cast<unsigned>((d.cw_off + 4256) * 4), static_cast<unsigned>(c4 * 16));                     // output conv weights
+        w[NI * d.gs + 1][0] = ldu1(cx.wb, static_cast<unsigned>((d.cw_off + 4320) * 4), 0u);
       }
     }
   }
@@ -681,20 +767,25 @@ __device__ __forceinline__ void prefetch_y(const Ctx& cx, int tid, f32x4 (&yp)[N
         constexpr int i = decltype(ii)::value, q = i & 3, n = (i >> 2) % d.NT, pt = (i >> 2) / d.NT;
         // (32x32 tiles: the sums live in HBM in accumulator order -- [wave task][pt][n][q][lane] float4 -- so that a wave's load /
         //  store is 1 KB contiguous; a [pos][channel] layout costs 32 partial lines per instruction)
-        yp[i] = ld_once(cx.ysr, r32_ys_off<I>(cx, t, pt, n, q) + static_cast<unsigned>(lane * 16));
+        // (everything but the lane's 16 bytes is wave-uniform: the task's block in the scalar base, the tile inside it in the immediate)
+        if constexpr (d.gs == 1) yp[i] = ldu_once(cx.ysr, static_cast<unsigned>(((pt * d.NT + n) * 4 + q) * 1024), r32_ys_off<I>(cx, t, 0, 0, 0), static_cast<unsigned>(lane * 16));
+        else yp[i] = ld_once(cx.ysr, r32_ys_off<I>(cx, t, pt, n, q) + static_cast<unsigned>(lane * 16));
       });
     } else if constexpr (d.epl == 1) {
       // one output element per lane (x_epilogue1): element e = [virtual position][packed channel], the thread's own
       constexpr int total = d.gs * d.P * ntot(d);
       const int e = tid < total ? tid : total - 1;
-      yp[0][0] = ld_once1(cx.ysr, x16_ys_off<I>(cx, e >> 2) + static_cast<unsigned>((e & 3) * 4));
+      if constexpr (d.gs == 1) yp[0][0] = ldu_once1(cx.ysr, static_cast<unsigned>(d.ys_off * 4), gofs(cx, d.g0), static_cast<unsigned>(e * 4));
+      else yp[0][0] = ld_once1(cx.ysr, x16_ys_off<I>(cx, e >> 2) + static_cast<unsigned>((e & 3) * 4));
     } else {
       constexpr int per = d.P * ntot(d) / 4, total = d.gs * per;
       sfor<yp_regs(I)>([&](auto ii) {
         constexpr int i = decltype(ii)::value;
         int item = tid + THREADS * i;
         if ((i + 1) * THREADS > total) item = item < total ? item : total - 1;
-        yp[i] = ld_once(cx.ysr, x16_ys_off<I>(cx, item));
+        if constexpr (d.gs == 1 && (i + 1) * THREADS <= total) yp[i] = ldu_once(cx.ysr, static_cast<unsigned>(d.ys_off * 4 + THREADS * i * 16), gofs(cx, d.g0), static_cast<unsigned>(tid * 16));
+        else if constexpr (d.gs == 1) yp[i] = ldu_once(cx.ysr, static_cast<unsigned>(d.ys_off * 4), gofs(cx, d.g0), static_cast<unsigned>(item * 16));
+        else yp[i] = ld_once(cx.ysr, x16_ys_off<I>(cx, item));
       });
     }
   }
@@ -706,10 +797,10 @@ __device__ __forceinline__ void ext_load(const Ctx& cx, int tid, f32x4 (&wx)[NX]
     constexpr OpD d = kOps[I];
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const Task t = conv_task<I>(wave);
-    const gcb_t wbase = cx.wb + static_cast<unsigned long long>(static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
+    const gcb_t wbase = ubase(cx.wb, static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
     sfor<ext_sf(I)>([&](auto ff) {
       constexpr int sf = carry_w(I) + decltype(ff)::value;
-      wx[decltype(ff)::value] = ldb(wbase + static_cast<unsigned long long>(sf * 1024), static_cast<unsigned>(lane * 16));
+      wx[decltype(ff)::value] = ldw<sf>(wbase, static_cast<unsigned>(lane * 16));
     });
   }
 }
@@ -799,8 +890,10 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
       const int vpos = u >> clog2(R);
       const int gi = d.gs > 1 ? vpos >> clog2(d.P) : 0, pos = d.gs > 1 ? vpos & (d.P - 1) : vpos;      // stream slot, position inside the stream
       const int eb = d.ex_b + vpos * OPB + (r * GC + 4 * li) * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      sfor<KS>([&](auto kk) { v += lds4(eb + (K0 + decltype(kk)::value) * (VP * OPB)); });
+      // (from the first slice, not from zero: `0 + x` is an instruction the compiler may not drop -- it differs from x for x = -0 -- and the sums
+      //  are the same bit for bit: an accumulator that starts at +0 never holds -0, so no slice does)
+      f32x4 v = lds4(eb + K0 * (VP * OPB));
+      sfor<KS - 1>([&](auto kk) { v += lds4(eb + (K0 + decltype(kk)::value + 1) * (VP * OPB)); });
       if constexpr (d.ys != 0) v += yp[ps];      // W[tap 0] x_{t-1}, computed by this op one frame ago
       v = v * wsc + bias;
       if constexpr (d.ln) {
@@ -817,7 +910,9 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
       const int row = pos * d.row_mul + d.row_add + r;
       const unsigned go = gofs(cx, d.g0 + gi);
       if constexpr (is_up(d)) FZ_TRACE4(cx, d.g0 + gi, 13 + d.bidx, row, 128, 4 * li, v);
-      if constexpr (CSUM) cs += v;
+      // (the first pass replaces the zero.  A row of -0 would leave -0 where `0 + row` left +0 -- and the CTFA adds the partial rows to a sum
+      //  that starts at +0, which absorbs either: its mean is the same bit for bit)
+      if constexpr (CSUM) { if constexpr (ps == 0) cs = v; else cs += v; }
       // (the rows of the next image first: the next op's MFMAs wait for them behind the barrier; the HBM copies are nobody's critical path,
       //  and a store that has to queue behind the op's prefetches at the memory pipe would hold the LDS writes back with it)
       if constexpr (d.fwd.on) { if (fwd_has<I>(gi)) fwd_st4g<I>(gi, row, 4 * li, v); }
@@ -842,8 +937,8 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
       if ((ps + 1) * NTHR <= total || FZ_LIKELY(item < total)) {
         const int u = item >> clog2(LPG), l2 = item & (LPG - 1);
         const int eb = d.ex_b + (u >> clog2(R)) * OPB + ((u & (R - 1)) * GC + 4 * l2) * 4;
-        f32x4 y = {0.f, 0.f, 0.f, 0.f};
-        sfor<KS>([&](auto kk) { y += lds4(eb + decltype(kk)::value * (VP * OPB)); });
+        f32x4 y = lds4(eb);
+        sfor<KS - 1>([&](auto kk) { y += lds4(eb + (decltype(kk)::value + 1) * (VP * OPB)); });
         st_next(cx.ysw, x16_ys_off<I>(cx, item), y);
       }
     });
@@ -876,8 +971,8 @@ __device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 
     const int vpos = u >> clog2(R);
     const int gi = d.gs > 1 ? vpos >> clog2(d.P) : 0, pos = d.gs > 1 ? vpos & (d.P - 1) : vpos;
     const int eb = d.ex_b + vpos * OPB + (r * GC + cch) * 4;
-    float v = 0.f;
-    sfor<KS>([&](auto kk) { v += lds1(eb + (K0 + decltype(kk)::value) * (VP * OPB)); });
+    float v = lds1(eb + K0 * (VP * OPB));      // (from the first slice: see x_epilogue)
+    sfor<KS - 1>([&](auto kk) { v += lds1(eb + (K0 + decltype(kk)::value + 1) * (VP * OPB)); });
     if constexpr (d.ys != 0) v += yp[0][0];      // W[tap 0] x_{t-1}, computed by this op one frame ago
     v = v * wsc + bias;
     if constexpr (d.ln) {
@@ -905,8 +1000,8 @@ __device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 
     if (FZ_LIKELY(item < items)) {
       const int uu = item >> clog2(LPG4), l2 = item & (LPG4 - 1);
       const int eb = d.ex_b + (uu >> clog2(R)) * OPB + ((uu & (R - 1)) * GC + 4 * l2) * 4;
-      f32x4 y = {0.f, 0.f, 0.f, 0.f};
-      sfor<KS>([&](auto kk) { y += lds4(eb + decltype(kk)::value * (VP * OPB)); });
+      f32x4 y = lds4(eb);
+      sfor<KS - 1>([&](auto kk) { y += lds4(eb + (decltype(kk)::value + 1) * (VP * OPB)); });
       st_next(cx.ysw, x16_ys_off<I>(cx, item), y);
     }
   }
@@ -949,7 +1044,7 @@ __device__ __forceinline__ void conv_x16b(const Ctx& cx, int tid, Carry<I>& c, c
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) { acc[pt][nt][pl] = f32x4{0.f, 0.f, 0.f, 0.f}; if constexpr (TWO) acco[pt][nt][pl] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  const gcb_t wbase = cx.wb + static_cast<unsigned long long>(static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
+  const gcb_t wbase = ubase(cx.wb, static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
   const unsigned lane16 = static_cast<unsigned>(lane * 16);
   if (t.active) pin_regs(c.w);
   FZ_STAMP(I, 5);
@@ -972,7 +1067,7 @@ __device__ __forceinline__ void conv_x16b(const Ctx& cx, int tid, Carry<I>& c, c
           }
         }
         if constexpr ((f % 2 == 1 || f + 1 == NF) && sf + CW < NSF) {
-          c.w[sf % CW] = ldb(wbase + static_cast<unsigned long long>((sf + CW) * 1024), lane16);
+          c.w[sf % CW] = ldw<sf + CW>(wbase, lane16);
           sched_pin();
         }
       });
@@ -1049,7 +1144,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
     for (int n = 0; n < NA; ++n)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[pt][n][e] = 0.f;
-  const gcb_t wbase = cx.wb + static_cast<unsigned long long>(static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
+  const gcb_t wbase = ubase(cx.wb, static_cast<unsigned>((d.w_off + t.wbase_f) * 4));
   const unsigned lane16 = static_cast<unsigned>(lane * 16);
   if (t.active) { pin_regs(c.w); if constexpr (EXT > 0) pin_regs(wx); }
   FZ_STAMP(I, 5);
@@ -1080,7 +1175,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
 #pragma unroll
           for (int pt = 0; pt < PT; ++pt) acc[pt][na] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[pt][pl], acc[pt][na], 0, 0, 0);
         if constexpr (EXT == 0 && (f % 2 == 1 || f + 1 == NF) && sf + CW < NSF) {
-          c.w[sf % CW] = ldb(wbase + static_cast<unsigned long long>((sf + CW) * 1024), lane16);
+          c.w[sf % CW] = ldw<sf + CW>(wbase, lane16);
           sched_pin();
         }
       });
@@ -1120,14 +1215,14 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
             for (int e = 0; e < 4; ++e) acc[pt][n][4 * q + e] += c.yp[(pt * NT + n) * 4 + q][e];
     }
   }
-  if constexpr (prm_dword(d)) { if (FZ_LIKELY(tid < nparams(d))) lds1(SCR_B + tid * 4) = c.prm[0]; }
-  else { if (FZ_LIKELY(tid < (nparams(d) + 3) / 4)) lds4(SCR_B + tid * 16) = c.prm; }
+  if constexpr (prm_dword(d)) { if (FZ_LIKELY(tid < nparams(d))) lds1s(SCR_B + tid * 4) = c.prm[0]; }
+  else { if (FZ_LIKELY(tid < (nparams(d) + 3) / 4)) lds4s(SCR_B + tid * 16) = c.prm; }
   FZ_STAMP(I, 1);
   lds_barrier();                      // every wave is done with this op's image; parameters are in LDS
   FZ_STAMP(I, 2);
   if (t.active && (!r32_two(d) || t.ks != 0)) {
     float alpha = 0.f;
-    if constexpr (d.ln) alpha = lds1(SCR_B + (2 * NTOT + 2 * d.gc) * 4);
+    if constexpr (d.ln) alpha = lds1s(SCR_B + (2 * NTOT + 2 * d.gc) * 4);
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
       const int pos = lane_p[pt], gi = lane_g[pt];      // position inside its stream, stream slot
@@ -1140,7 +1235,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
           const int nb = 32 * (t.b * NT + n);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x4 bi = lds4(SCR_B + (nb + 8 * q + 4 * h) * 4), sc = lds4(SCR_B + (NTOT + nb + 8 * q + 4 * h) * 4);
+            const f32x4 bi = lds4s(SCR_B + (nb + 8 * q + 4 * h) * 4), sc = lds4s(SCR_B + (NTOT + nb + 8 * q + 4 * h) * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { acc[pt][n][4 * q + e] = acc[pt][n][4 * q + e] * sc[e] + bi[e]; s += acc[pt][n][4 * q + e]; }
           }
@@ -1157,8 +1252,8 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
           const int c0 = (32 * (t.b * NT + n)) & (d.gc - 1);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x4 gm = lds4(SCR_B + (2 * NTOT + c0 + 8 * q + 4 * h) * 4);
-            const f32x4 bt = lds4(SCR_B + (2 * NTOT + d.gc + c0 + 8 * q + 4 * h) * 4);
+            const f32x4 gm = lds4s(SCR_B + (2 * NTOT + c0 + 8 * q + 4 * h) * 4);
+            const f32x4 bt = lds4s(SCR_B + (2 * NTOT + d.gc + c0 + 8 * q + 4 * h) * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float y = acc[pt][n][4 * q + e] * rstd * gm[e] + bt[e];
@@ -1172,7 +1267,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
           const int nb = UP ? ((n / NT) * d.N + 32 * (t.b * NT + n % NT)) : 32 * (t.b * NT + n);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x4 bi = lds4(SCR_B + (nb + 8 * q + 4 * h) * 4), sc = lds4(SCR_B + (NTOT + nb + 8 * q + 4 * h) * 4);
+            const f32x4 bi = lds4s(SCR_B + (nb + 8 * q + 4 * h) * 4), sc = lds4s(SCR_B + (NTOT + nb + 8 * q + 4 * h) * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[pt][n][4 * q + e] = acc[pt][n][4 * q + e] * sc[e] + bi[e];
           }
@@ -1207,12 +1302,12 @@ __device__ __forceinline__ void input_op(const Ctx& cx, int tid) {
   constexpr OpD d = kOps[I];
   static_assert(d.gs == 1, "the input layer runs one stream at a time");
   const int c4 = tid & 15;
-  const unsigned pb = static_cast<unsigned>(d.p_off * 4 + c4 * 16);
-  const f32x4 w = ldb(cx.wb, pb), bb = ldb(cx.wb, pb + 256), gm = ldb(cx.wb, pb + 512), bt = ldb(cx.wb, pb + 768);
-  const float alpha = ldb1(cx.wb, static_cast<unsigned>(d.p_off * 4 + 1024));
+  const unsigned pb = static_cast<unsigned>(d.p_off * 4), c16 = static_cast<unsigned>(c4 * 16);
+  const f32x4 w = ldu(cx.wb, pb, c16), bb = ldu(cx.wb, pb + 256, c16), gm = ldu(cx.wb, pb + 512, c16), bt = ldu(cx.wb, pb + 768, c16);
+  const float alpha = ldu1(cx.wb, pb + 1024, 0u);
   float x[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) x[i] = cx.io_in[d.g0 * 256 + (tid >> 4) + 32 * i];
+  for (int i = 0; i < 8; ++i) x[i] = ldu1((gcb_t)cx.io_in, static_cast<unsigned>((d.g0 * 256 + 32 * i) * 4), static_cast<unsigned>((tid >> 4) * 4));
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int pos = (tid >> 4) + 32 * i;
@@ -1312,11 +1407,11 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
   for (int k = 0; k < 21; ++k) asm volatile("" : "+v"(wd[k]));
   if (tid < 21 * GS) {          // thread (stream slot gi, unit uu): the unit's four gates
     const int gi = GS > 1 ? tid / 21 : 0, uu = GS > 1 ? tid % 21 : tid;
-    f32x4 zz[4];
+    f32x4 zz[4];      // (each chain starts from its first partial row -- a sum of FMAs from +0, never -0: adding it to zero changes nothing)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) zz[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) zz[q] = lds4(PART + gi * SGB + (q * 21 + uu) * 16);
 #pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) zz[s2 & 3] += lds4(PART + gi * SGB + (s2 * 21 + uu) * 16);      // (four chains: the partial rows are not one dependent sum)
+    for (int s2 = 4; s2 < 16; ++s2) zz[s2 & 3] += lds4(PART + gi * SGB + (s2 * 21 + uu) * 16);      // (four chains: the partial rows are not one dependent sum)
     f32x4 zh = lds4(PART + gi * SGB + (16 * 21 + uu) * 16) + lds4(PART + gi * SGB + (17 * 21 + uu) * 16);
     zh += lds4(PART + gi * SGB + (18 * 21 + uu) * 16) + lds4(PART + gi * SGB + (19 * 21 + uu) * 16);
     const f32x4 z = c.w[S0 + 8] + ((zz[0] + zz[1]) + (zz[2] + zz[3])) * c.w[S0 + 9][1] + zh * c.w[S0 + 9][2];
@@ -1340,12 +1435,15 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
     const int idx = tid + THREADS * ps;
     if (idx < d.dout * GS) {
       const int gi = GS > 1 ? idx >> clog2(d.dout) : 0, n = GS > 1 ? idx & (d.dout - 1) : tid;
+      // (the roundings spelled out -- one product rounded, the other fused into the sum of the two -- as the compiler has always contracted
+      //  `w0 h0 + w1 h1`: left to it, which of the pairs it fuses depends on how it happens to vectorise the two chains, and the rows change in
+      //  their last bit with any unrelated edit of this function: tests/test_gpu_fused_bitexact.py)
       float a0 = 0.f, a1 = 0.f;
 #pragma unroll
       for (int q = 0; q < 5; ++q) {
         const f32x4 h4 = lds4(HN + gi * SGB + 16 * q);
-        a0 += wd[4 * q] * h4[0] + wd[4 * q + 1] * h4[1];
-        a1 += wd[4 * q + 2] * h4[2] + wd[4 * q + 3] * h4[3];
+        a0 += __builtin_fmaf(wd[4 * q], h4[0], wd[4 * q + 1] * h4[1]);
+        a1 += __builtin_fmaf(wd[4 * q + 2], h4[2], wd[4 * q + 3] * h4[3]);
       }
       a0 = fmaf(wd[20], lds1(HN + gi * SGB + 80), a0);
       const float a = DI8 ? fmaf(a0 + a1, sd, bd) : (a0 + a1) + bd;
@@ -1410,17 +1508,18 @@ __device__ __forceinline__ void gates_load(const Ctx& cx, int tid, f32x4 (&g)[17
   constexpr OpD d = kOps[J];
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < d.gs) {
+    const unsigned l64 = static_cast<unsigned>(lane * 64);      // (the lane's 16 weights of a matrix)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      g[q] = ldb(cx.wb, static_cast<unsigned>((d.cw_off + lane * 16 + 4 * q) * 4));
-      g[4 + q] = ldb(cx.wb, static_cast<unsigned>((d.cw_off + 1040 + lane * 16 + 4 * q) * 4));
-      g[8 + q] = ldb(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + lane * 16 + 4 * q) * 4));
-      g[12 + q] = ldb(cx.wb, static_cast<unsigned>((d.cw_off + 3168 + lane * 16 + 4 * q) * 4));
+      g[q] = ldu(cx.wb, static_cast<unsigned>((d.cw_off + 4 * q) * 4), l64);
+      g[4 + q] = ldu(cx.wb, static_cast<unsigned>((d.cw_off + 1040 + 4 * q) * 4), l64);
+      g[8 + q] = ldu(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + 4 * q) * 4), l64);
+      g[12 + q] = ldu(cx.wb, static_cast<unsigned>((d.cw_off + 3168 + 4 * q) * 4), l64);
     }
-    g[16][0] = ldb1(cx.wb, static_cast<unsigned>((d.cw_off + 1024 + (lane & 15)) * 4));
-    g[16][1] = ldb1(cx.wb, static_cast<unsigned>((d.cw_off + 2064 + lane) * 4));
-    g[16][2] = ldb1(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + 1024 + (lane & 15)) * 4));
-    g[16][3] = ldb1(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + 2064 + lane) * 4));
+    g[16][0] = ldu1(cx.wb, static_cast<unsigned>((d.cw_off + 1024) * 4), static_cast<unsigned>((lane & 15) * 4));
+    g[16][1] = ldu1(cx.wb, static_cast<unsigned>((d.cw_off + 2064) * 4), static_cast<unsigned>(lane * 4));
+    g[16][2] = ldu1(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + 1024) * 4), static_cast<unsigned>((lane & 15) * 4));
+    g[16][3] = ldu1(cx.wb, static_cast<unsigned>((d.cw_off + 2128 + 2064) * 4), static_cast<unsigned>(lane * 4));
   } else {
     opaque_regs(g);
   }
@@ -1455,7 +1554,7 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
   if (wave < GS) {
     // frequency branch: the sum of the time attention over the 31 frames before this one (causal32 mode; a vector of zeros in the
     // default frame mode, where the branch sees TA / 32 -- SURVEY F7), stage d.bidx of this wave's stream
-    ta_prev = ldb1(cx.ta_sum, static_cast<unsigned>(((cx.stream + d.g0 + wave) * cx.ta_sum_sstride + d.bidx * cx.ta_sum_gstride + lane) * 4));
+    ta_prev = *(gcf_t)(ubase(cx.ta_sum, static_cast<unsigned>(((cx.stream + d.g0 + wave) * cx.ta_sum_sstride + d.bidx * cx.ta_sum_gstride) * 4)) + static_cast<unsigned long long>(static_cast<unsigned>(lane * 4)));
   }
   const f32x4 ow = c.w[NI * GS];
   const float ob = c.w[NI * GS + 1][0];
@@ -1465,11 +1564,12 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
 #pragma unroll
     for (int gi = 0; gi < GS; ++gi) {
       f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
+      sfor<NI>([&](auto ii) {
+        constexpr int i = decltype(ii)::value;
         const int f = rg + 32 * i;
-        if (f < d.F) s4 += fwd_ld4g<I>(gi, f, 4 * c4);
-      }
+        // (the first row replaces the zero; a column of -0 then leaves -0 where `0 + row` left +0, and the sum `m` below, which starts at +0, absorbs it)
+        if (f < d.F) { if constexpr (i == 0) s4 = fwd_ld4g<I>(gi, f, 4 * c4); else s4 += fwd_ld4g<I>(gi, f, 4 * c4); }
+      });
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         s4[e] = xor32_sum(xor16_sum(s4[e]));
@@ -1511,7 +1611,7 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
         FZ_TRACE4(cx, d.g0 + gi, 1 + d.bidx, f, 64, 4 * c4, y);
         if constexpr (d.last) {
           const float s = group_sum<16>(y[0] * ow[0] + y[1] * ow[1] + y[2] * ow[2] + y[3] * ow[3]);
-          if (c4 == 0) cx.io_out[(d.g0 + gi) * 256 + f] = s + ob;
+          if (c4 == 0) stu1((gcb_t)(unsigned long long)cx.io_out, static_cast<unsigned>(((d.g0 + gi) * 256 + 32 * i) * 4), static_cast<unsigned>(rg * 4), s + ob);
         } else {
           fwd_st4g<I>(gi, f, 4 * c4, y);
           // (packed plans: a consumer that is not the next op of this stream reads the rows from HBM)
@@ -1912,6 +2012,16 @@ __global__ __launch_bounds__(THREADS) void FZ_KERNEL(const FzArgs a) {
   if (PROF && cx.prof && threadIdx.x == 0) cx.prof[kNumOps] = wall_clock64();
 }
 
+// The LDS accessors address the dynamic block by number, from byte 0: a build whose kernel has static LDS in front of it is refused here, when
+// the handle is created, not found out by its results.
+static hipError_t fz_set_lds() {
+  hipFuncAttributes fa;
+  hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(FZ_KERNEL));
+  if (e != hipSuccess) return e;
+  if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(FZ_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+}
+
 }  // namespace fz
 
 #if FZ_PROF
@@ -1922,7 +2032,7 @@ hipError_t FZ_LAUNCH(float* arena, long long sstride, const float* blob, const f
   return hipGetLastError();
 }
 hipError_t FZ_ATTR() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(fz::FZ_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
+  return fz::fz_set_lds();
 }
 #elif defined(FZ_NO_PROF_TWIN)
 // packed builds: `grid` workgroups of kStreams streams each.  A profiling twin exists only as an optional translation unit (weak
@@ -1945,7 +2055,7 @@ hipError_t FZ_LAUNCH(float* arena, long long sstride, const float* blob, const f
   return hipGetLastError();
 }
 hipError_t FZ_ATTR() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fz::FZ_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
+  hipError_t e = fz::fz_set_lds();
 #ifdef FZ_OPT_PROF_ATTR
   if (e == hipSuccess && FZ_OPT_PROF_ATTR) e = FZ_OPT_PROF_ATTR();
 #endif
@@ -1963,7 +2073,7 @@ hipError_t FZ_LAUNCH(float* arena, long long sstride, const float* blob, const f
   return hipGetLastError();
 }
 hipError_t FZ_ATTR() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fz::FZ_KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
+  hipError_t e = fz::fz_set_lds();
   return e != hipSuccess ? e : FZ_ATTR_PROF();
 }
 #endif
