@@ -315,8 +315,8 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * An offline handle gets NUTLS_ERR_ARG from the hop entries, a streaming handle from the block entries.
  * The _host entries copy the raw samples (pageable or nutls_host_alloc) into library buffers, run the pipeline and copy back; they
  * synchronise like their float twins -- int16 moves half the bytes over the link.  nutls_enhance_hop_pcm_host_active hands its mask on as
- * a device mask (see nutls_step_active on nutls_state_set and masks the host has not seen).  No zero-copy reads of pinned PCM, no ragged
- * blocks in the callers' format: nutls_enhance_block_ragged stays at float32 and 16 kHz. */
+ * a device mask (see nutls_step_active on nutls_state_set and masks the host has not seen).  Ragged blocks in the callers' format: the
+ * _pcm_ragged entries at the end of this section.  Zero-copy reads of pinned PCM stay out of scope: the _host entries copy. */
 #define NUTLS_PCM_F32 0   /* float32, unit scale (what nutls_enhance_hop takes) */
 #define NUTLS_PCM_S16 1   /* int16, little endian; 32768 = 1.0 */
 int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);
@@ -340,6 +340,27 @@ int nutls_enhance_block_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, 
 int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode);
 int nutls_pcm_decode_block(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, void* stream);
 int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, void* stream);
+/* Ragged blocks in the callers' format: "Ragged blocks" above, with hops of S samples of the handle's sample type.  pcm_in / pcm_out:
+ * [utterances, n_hops * S], base pointer 16-byte aligned; hops: [utterances] int, hops[u] = k in 0 .. n_hops LEADING real hops of utterance u.
+ * nutls_enhance_block_pcm_ragged decodes with the counts, calls nutls_enhance_block_ragged on the library's float buffers and encodes with
+ * the counts.  For utterance u, one call
+ *   - writes hops 0 .. k-1 of pcm_out with exactly the bits nutls_enhance_block_pcm of the same width writes there;
+ *   - writes hops k .. n_hops-1 of pcm_out with ZEROS; the matching hops of pcm_in are not read and may hold anything (NaN, any int16).  The
+ *     caller's input buffer is never written;
+ *   - carries the resampler history of both directions from hop k-1, and what nutls_enhance_block_ragged carries from frame k;
+ *   - k = 0 HOLDS the utterance completely: both resampler histories, the previous hop, the overlap tail and the model state stay as they were.
+ * Any cut of a recording into ragged calls gives the same concatenated samples, bit for bit.  hops == NULL: the call IS the entry without
+ * counts (same code path, same bits).  At 16000 / NUTLS_PCM_F32 the two enhance entries ARE nutls_enhance_block_ragged / _ragged_host.
+ * Device entries: hops is a DEVICE pointer that the kernels read and clamp to 0 .. n_hops (the host does not synchronise to look); it stays
+ * valid and unmodified until the work queued on `stream` has run.  The _host entry takes pcm_in, pcm_out and hops in HOST memory; a count
+ * outside 0 .. n_hops, a bad dc_mode or n_hops, a null pointer or a streaming handle is NUTLS_ERR_ARG (nutls_last_error says which), checked
+ * before anything is converted: a refused call leaves every history where it was.  The two halves: nutls_pcm_decode_block /
+ * nutls_pcm_encode_block with counts; the 16 kHz side is [utterances, n_hops * 256] float32, its hops behind a count are zeros.
+ * Cost: the uniform entry's (the kernels return early behind a count; the model computes and discards, see "Ragged blocks"). */
+int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
+int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode);
+int nutls_pcm_decode_block_ragged(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, const int* hops, void* stream);
+int nutls_pcm_encode_block_ragged(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, const int* hops, void* stream);
 
 /* Library-owned device staging buffers [B,256]; stepping on them avoids the D2D copies and lets
  * the captured hipGraph run with no per-call parameter update. */

@@ -51,6 +51,18 @@ int build_offline_plan(Engine* e) {
   return dev_alloc(e, static_cast<size_t>(e->outt) * 12 * (31 + e->offline) * 64, &e->ta_hist, true);      // [utterance][stage][31 + frame][64]
 }
 
+// The counts of a _host entry: checked (nothing is touched when one is out of range), then copied to the handle's device buffer on the
+// library's stream, in front of the work that reads them.
+int upload_counts(Engine* e, const int* counts, int n, const char* who) {
+  for (int u = 0; u < e->outt; ++u)
+    if (counts[u] < 0 || counts[u] > n)
+      return fail(NUTLS_ERR_ARG, std::string(who) + ": count " + std::to_string(counts[u]) + " of utterance " + std::to_string(u) + " is outside 0 .. " + std::to_string(n));
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = dev_alloc_once(e, static_cast<size_t>(e->outt), &e->d_counts, false)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_counts, counts, static_cast<size_t>(e->outt) * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  return NUTLS_OK;
+}
+
 }  // namespace nutls
 
 using namespace nutls;
@@ -320,18 +332,6 @@ int nutls_process_block(nutls_handle* h, const float* mag_in, float* mag_out, in
 
 int nutls_process_block_ragged(nutls_handle* h, const float* mag_in, float* mag_out, int n_frames, const int* frames, void* stream) {
   return process_block_impl(h, mag_in, mag_out, n_frames, frames, false, stream, frames ? "nutls_process_block_ragged" : "nutls_process_block");
-}
-
-// The counts of a _host entry: checked (nothing is touched when one is out of range), then copied to the handle's device buffer on the
-// library's stream, in front of the work that reads them.
-static int upload_counts(Engine* e, const int* counts, int n, const char* who) {
-  for (int u = 0; u < e->outt; ++u)
-    if (counts[u] < 0 || counts[u] > n)
-      return fail(NUTLS_ERR_ARG, std::string(who) + ": count " + std::to_string(counts[u]) + " of utterance " + std::to_string(u) + " is outside 0 .. " + std::to_string(n));
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = dev_alloc_once(e, static_cast<size_t>(e->outt), &e->d_counts, false)) return rc;
-  HIP_TRY(hipMemcpyAsync(e->d_counts, counts, static_cast<size_t>(e->outt) * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  return NUTLS_OK;
 }
 
 int nutls_stft_block(nutls_handle* h, const float* pcm_in, float* mag, int n_hops, void* stream) {

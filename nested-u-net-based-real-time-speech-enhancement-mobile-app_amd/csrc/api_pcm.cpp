@@ -3,7 +3,10 @@
 // offline ones.  Every entry here decodes into a library float32 buffer at 16 kHz, calls the existing entry (nutls_enhance_hop,
 // nutls_enhance_hop_active, nutls_enhance_block) on library buffers and encodes: the model path, the masks, hop fusion and the state
 // coherence are that code, not copies of it.  At 16000 / float32 the entries ARE the plain ones (forwarded before anything else happens).
+// The _pcm_ragged block entries do the same around nutls_enhance_block_ragged, with the per-utterance hop counts handed to both kernels.
 // The kernels: pcm.hip.
+#include <cstdint>
+
 #include "engine.hpp"
 
 using namespace nutls;
@@ -50,18 +53,19 @@ int zero_histories(Engine* e, int idx) {
 }
 
 // One launch of a half.  A block call (offline handle) flips the history buffers; a hop call (streaming handle) works in place on buffer 0.
-int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s) {
+// counts: the DEVICE counts of a ragged block or null (the flip is the whole handle's: the kernel carries a held row's history across).
+int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
-  HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
   st.dec_par = nxt;
   return NUTLS_OK;
 }
 
-int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s) {
+int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
-  HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
   st.enc_par = nxt;
   return NUTLS_OK;
 }
@@ -144,6 +148,25 @@ int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops,
   if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, nullptr, n_hops, s)) return rc;
   if (int rc = nutls_enhance_block(h, e->pcm.f_in, e->pcm.f_out, n_hops, dc_mode, stream)) return rc;
   return encode_launch(e, e->pcm.f_out, pcm_out, nullptr, n_hops, s);
+}
+
+// The ragged block: the three parts of block_device, each with the DEVICE counts `hops` (not null).  The decode writes zero hops behind the
+// counts into the library's buffer, nutls_enhance_block_ragged reads none of them and writes zeros there, the encode reads none of those.
+int block_device_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, nullptr, n_hops, s, hops)) return rc;
+  if (int rc = nutls_enhance_block_ragged(h, e->pcm.f_in, e->pcm.f_out, n_hops, hops, dc_mode, stream)) return rc;
+  return encode_launch(e, e->pcm.f_out, pcm_out, nullptr, n_hops, s, hops);
+}
+
+// the 16-byte alignment nutls.h asks of every _pcm buffer is checked where counts come with it, as the ragged float entries do
+int aligned16(const void* a, const void* b, const char* who) {
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": with hop counts the buffers must be 16-byte aligned");
+  return NUTLS_OK;
 }
 
 }  // namespace
@@ -293,6 +316,61 @@ int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out,
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = pcm_init(e)) return rc;
   return encode_launch(e, wave_in, pcm_out, nullptr, n_hops, static_cast<hipStream_t>(stream));
+}
+
+// ---- offline handles, ragged: per-utterance hop counts in the callers' format ------------------------------------------------------------------
+int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  const char* who = "nutls_enhance_block_pcm_ragged";
+  if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  if (plain_format(&h->eng))
+    return nutls_enhance_block_ragged(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, hops, dc_mode, stream);
+  if (!hops) return nutls_enhance_block_pcm(h, pcm_in, pcm_out, n_hops, dc_mode, stream);
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;
+  if (int rc = dc_ok(dc_mode, who)) return rc;
+  if (int rc = aligned16(pcm_in, pcm_out, who)) return rc;
+  return block_device_ragged(h, pcm_in, pcm_out, n_hops, hops, dc_mode, stream);
+}
+
+// hops: HOST.  Every refusal, the counts' included, comes before the first conversion: a refused call leaves the histories where they were.
+int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode) {
+  const char* who = "nutls_enhance_block_pcm_ragged_host";
+  if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  if (plain_format(&h->eng))
+    return nutls_enhance_block_ragged_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, hops, dc_mode);
+  if (!hops) return nutls_enhance_block_pcm_host(h, pcm_in, pcm_out, n_hops, dc_mode);
+  if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;
+  if (int rc = dc_ok(dc_mode, who)) return rc;
+  Engine* e = &h->eng;
+  if (int rc = upload_counts(e, hops, n_hops, who)) return rc;
+  if (int rc = pcm_init(e)) return rc;
+  if (int rc = raw_init(e)) return rc;
+  // (the rows behind the counts cross the link too: the kernels do not read them on the device)
+  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * hop_samples(e) * sample_bytes(e);
+  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = block_device_ragged(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, e->d_counts, dc_mode, e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return NUTLS_OK;
+}
+
+int nutls_pcm_decode_block_ragged(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, const int* hops, void* stream) {
+  if (!hops) return nutls_pcm_decode_block(h, pcm_in, wave_out, n_hops, stream);
+  if (int rc = block_args(h, pcm_in && wave_out, n_hops, "nutls_pcm_decode_block_ragged")) return rc;
+  if (int rc = aligned16(pcm_in, wave_out, "nutls_pcm_decode_block_ragged")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return decode_launch(e, pcm_in, wave_out, nullptr, n_hops, static_cast<hipStream_t>(stream), hops);
+}
+
+int nutls_pcm_encode_block_ragged(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, const int* hops, void* stream) {
+  if (!hops) return nutls_pcm_encode_block(h, wave_in, pcm_out, n_hops, stream);
+  if (int rc = block_args(h, wave_in && pcm_out, n_hops, "nutls_pcm_encode_block_ragged")) return rc;
+  if (int rc = aligned16(wave_in, pcm_out, "nutls_pcm_encode_block_ragged")) return rc;
+  Engine* e = &h->eng;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = pcm_init(e)) return rc;
+  return encode_launch(e, wave_in, pcm_out, nullptr, n_hops, static_cast<hipStream_t>(stream), hops);
 }
 
 }  // extern "C"

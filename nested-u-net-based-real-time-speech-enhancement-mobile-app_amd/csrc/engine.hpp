@@ -237,6 +237,9 @@ int check_hop_fusion(const Engine* e, const char* who);
 
 // ---- api_block.cpp ---------------------------------------------------------------------------
 int build_offline_plan(Engine* e);
+// The HOST counts of a ragged _host entry (`who`): checked -- one outside 0 .. n is NUTLS_ERR_ARG and nothing has been touched --, then copied
+// to e->d_counts on the library's stream, in front of the work that reads them.
+int upload_counts(Engine* e, const int* counts, int n, const char* who);
 
 // ---- api_pcm.cpp -----------------------------------------------------------------------------
 // nutls_reset: zero the resampler histories of row `idx` (stream / utterance; < 0: every row's) where they exist

@@ -11,6 +11,9 @@
 //      the sample lies in its hop, in its block or in which entry runs it: results are bit-exact across every cut of a stream;
 //   4. the hop leaves through LDS in 16-byte stores (float32 -> int16: y * 32768 rounded to nearest even, clamped, NaN -> 0).
 // A held row (active[row] == 0) returns before 1.: its history is neither read nor written, its output hop is zeros.
+// Ragged blocks (counts[row] = k real hops of the row, clamped to 0 .. n_hops): the hops in front of k run 1. to 4. as they are, the workgroup
+// of hop k - 1 writes the history, a hop behind k returns before 1. with a zero hop; k == 0 holds the row, and because a block call flips the
+// history buffers of the whole handle, the workgroup of its hop 0 copies the row's history across.
 // Cost: 256 * 145 FMAs per stream and hop at most (48 kHz decode); the launch, not the arithmetic, is what a hop pays for.
 #include <hip/hip_runtime.h>
 
@@ -106,7 +109,7 @@ __device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
 // ---- one hop of one row: NIN samples in, NIN / Q (DOWN) or NIN * Q (UP) out --------------------------------------------------------------------
 template <int Q, bool UP, int NIN, typename TI, typename TO>
 __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                        int n_hops) {
+                                        const int* counts, int n_hops) {
   constexpr int K = Rate<Q>::k;
   constexpr int HIST = UP ? 2 * K : 2 * K * Q;      // samples of left context
   constexpr int NOUT = UP ? NIN * Q : NIN / Q;
@@ -121,6 +124,18 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
     zero_out(dst, NOUT, tid);
     return;
   }
+  const int k = counts ? min(max(counts[row], 0), n_hops) : n_hops;      // the row's real hops (the whole workgroup: the count is per row)
+  if (t >= k) {      // behind the count: the input row is not read
+    zero_out(dst, NOUT, tid);
+    if constexpr (HIST > 0) {
+      if (k == 0 && t == 0) {      // a held row: its history moves to the buffer the next call reads
+        const f32x4* const from = reinterpret_cast<const f32x4*>(hist_in + static_cast<size_t>(row) * kPcmMaxHist);
+        f32x4* const to = reinterpret_cast<f32x4*>(hist_out + static_cast<size_t>(row) * kPcmMaxHist);
+        for (int i = tid; i < HIST / 4; i += kThreads) to[i] = from[i];
+      }
+    }
+    return;
+  }
   const TI* const src = in + (static_cast<size_t>(row) * n_hops + t) * NIN;
   for (int i = tid; i < Rate<Q>::taps; i += kThreads) s_p[i] = taps[i];
   if constexpr (HIST > 0) {
@@ -130,8 +145,8 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
   stage_in(src, s_x + HIST, NIN, tid);
   __syncthreads();
   if constexpr (HIST > 0) {
-    // the history the next call starts from.  hist_out may be hist_in only where this workgroup is also the one that read it (n_hops == 1)
-    if (t == n_hops - 1) stage_out(s_x + NIN, hist_out + static_cast<size_t>(row) * kPcmMaxHist, HIST, tid);
+    // the history the next call starts from: the row's last real hop's.  hist_out may be hist_in only where this workgroup is also the one that read it (n_hops == 1)
+    if (t == k - 1) stage_out(s_x + NIN, hist_out + static_cast<size_t>(row) * kPcmMaxHist, HIST, tid);
   }
   for (int n = tid; n < NOUT; n += kThreads) s_y[n] = pcm_fir<Q, UP>(s_p, s_x, n);
   __syncthreads();
@@ -141,30 +156,30 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
 // caller samples -> 16 kHz float32: a rate above 16 kHz is reduced, 8 kHz is doubled
 template <int Q, bool UP, typename TI>
 __global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
-                                                              const unsigned char* active, int n_hops) {
-  pcm_hop<Q, UP, UP ? 256 / Q : 256 * Q, TI, float>(in, out, taps, hist_in, hist_out, active, n_hops);
+                                                              const unsigned char* active, const int* counts, int n_hops) {
+  pcm_hop<Q, UP, UP ? 256 / Q : 256 * Q, TI, float>(in, out, taps, hist_in, hist_out, active, counts, n_hops);
 }
 
 // 16 kHz float32 -> caller samples
 template <int Q, bool UP, typename TO>
 __global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
-                                                              const unsigned char* active, int n_hops) {
-  pcm_hop<Q, UP, 256, float, TO>(in, out, taps, hist_in, hist_out, active, n_hops);
+                                                              const unsigned char* active, const int* counts, int n_hops) {
+  pcm_hop<Q, UP, 256, float, TO>(in, out, taps, hist_in, hist_out, active, counts, n_hops);
 }
 
 template <int Q, bool UP, typename T>
-hipError_t decode_as(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active, int rows,
-                     int n_hops, hipStream_t s) {
+hipError_t decode_as(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                     const int* counts, int rows, int n_hops, hipStream_t s) {
   hipLaunchKernelGGL((pcm_decode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out,
-                     active, n_hops);
+                     active, counts, n_hops);
   return hipGetLastError();
 }
 
 template <int Q, bool UP, typename T>
-hipError_t encode_as(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active, int rows,
-                     int n_hops, hipStream_t s) {
+hipError_t encode_as(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                     const int* counts, int rows, int n_hops, hipStream_t s) {
   hipLaunchKernelGGL((pcm_encode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out,
-                     active, n_hops);
+                     active, counts, n_hops);
   return hipGetLastError();
 }
 
@@ -210,10 +225,10 @@ std::vector<float> pcm_design(int rate_hz) {
 }
 
 hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
 #define NUTLS_PCM_DECODE(Q, UP) \
-  return s16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s) \
-             : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s)
+  return s16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
+             : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
   switch (rate_hz) {
     case 8000: NUTLS_PCM_DECODE(2, true);
     case 16000: NUTLS_PCM_DECODE(1, false);
@@ -225,10 +240,10 @@ hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, cons
 }
 
 hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
 #define NUTLS_PCM_ENCODE(Q, UP) \
-  return s16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s) \
-             : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, rows, n_hops, s)
+  return s16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
+             : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
   switch (rate_hz) {
     case 8000: NUTLS_PCM_ENCODE(2, false);
     case 16000: NUTLS_PCM_ENCODE(1, false);

@@ -42,11 +42,13 @@ struct PcmState {
 
 // Caller samples -> 16 kHz float32.  grid (n_hops, rows).  in: [rows, n_hops * S] of the format; out: [rows, n_hops * 256].  hist_in / hist_out:
 // [rows][kPcmMaxHist]; they may be the same buffer when n_hops == 1.  active (device, [rows], may be null): a held row's history is not touched,
-// its input is not read, its output hop is zeros.
+// its input is not read, its output hop is zeros.  counts (device, [rows], may be null: every row has n_hops): the row's leading real hops, clamped
+// by the kernel to 0 .. n_hops -- the hops behind a count are zeros and their input is not read, the new history is that of the last real hop,
+// and a row of count 0 has its history copied from hist_in to hist_out (with counts the two must be different buffers).
 hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
+                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
 // 16 kHz float32 -> caller samples; the same conventions the other way round.
 hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
+                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
 
 }  // namespace nutls

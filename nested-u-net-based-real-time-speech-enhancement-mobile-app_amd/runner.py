@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "nutls_enhance_hop_pcm", "nutls_enhance_hop_pcm_active", "nutls_enhance_hop_pcm_host", "nutls_enhance_hop_pcm_host_active",
     "nutls_pcm_decode_hop", "nutls_pcm_encode_hop",
     "nutls_enhance_block_pcm", "nutls_enhance_block_pcm_host", "nutls_pcm_decode_block", "nutls_pcm_encode_block",
+    "nutls_enhance_block_pcm_ragged", "nutls_enhance_block_pcm_ragged_host", "nutls_pcm_decode_block_ragged", "nutls_pcm_encode_block_ragged",
 )
 
 
@@ -153,6 +154,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_enhance_block_pcm_host.argtypes = [vp, vp, vp, c.c_int, c.c_int]
         lib.nutls_pcm_decode_block.argtypes = [vp, vp, vp, c.c_int, vp]
         lib.nutls_pcm_encode_block.argtypes = [vp, vp, vp, c.c_int, vp]
+    if not dev_lib or hasattr(lib, "nutls_enhance_block_pcm_ragged"):
+        vp = c.c_void_p
+        lib.nutls_enhance_block_pcm_ragged.argtypes = [vp, vp, vp, c.c_int, vp, c.c_int, vp]
+        lib.nutls_enhance_block_pcm_ragged_host.argtypes = [vp, vp, vp, c.c_int, c.POINTER(c.c_int), c.c_int]
+        lib.nutls_pcm_decode_block_ragged.argtypes = [vp, vp, vp, c.c_int, vp, vp]
+        lib.nutls_pcm_encode_block_ragged.argtypes = [vp, vp, vp, c.c_int, vp, vp]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -1009,17 +1016,23 @@ class NutlsOffline(_PcmFormat):
             raise ValueError("%s must be [%d, n_hops*%d] with 1 <= n_hops <= %d" % (name, self.utterances, unit, self.max_frames))
         return cols // unit
 
-    def enhance_block_pcm_device(self, pcm, out=None, dc_mode: str = "edge"):
+    def enhance_block_pcm_device(self, pcm, out=None, dc_mode: str = "edge", hops=None):
         """``enhance_block_device`` in the format of ``set_pcm_format``: ``pcm [utterances, n_hops * pcm_hop_samples]`` CUDA tensor of the
         handle's sample type -> the enhanced block in the same format (``nutls_enhance_block_pcm``), ``pcm_delay_samples`` plus one hop late;
-        the resampler histories carry from block to block."""
+        the resampler histories carry from block to block.  ``hops``: per-utterance counts as in :meth:`enhance_block_device`
+        (``nutls_enhance_block_pcm_ragged``): the hops behind a count are never read and come back as zeros, every history of the
+        utterance carries on from its last real hop, a count of 0 holds it."""
         import torch
         dc = self._dc(dc_mode)
         S = self.pcm_hop_samples
         n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
         x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
         o = torch.empty_like(x) if out is None else self._pcm_tensor(out, self.utterances, n * S, "out")
-        _check(self._lib, self._lib.nutls_enhance_block_pcm(self._h, x.data_ptr(), o.data_ptr(), n, dc, torch.cuda.current_stream(x.device).cuda_stream))
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if hops is None:
+            _check(self._lib, self._lib.nutls_enhance_block_pcm(self._h, x.data_ptr(), o.data_ptr(), n, dc, stream))
+        else:
+            _check(self._lib, self._lib.nutls_enhance_block_pcm_ragged(self._h, x.data_ptr(), o.data_ptr(), n, self._device_counts(hops, n, x, "hops"), dc, stream))
         return o
 
     def enhance_block_pcm_host(self, pcm: np.ndarray, out: Optional[np.ndarray] = None, dc_mode: str = "edge") -> np.ndarray:
@@ -1032,27 +1045,36 @@ class NutlsOffline(_PcmFormat):
         _check(self._lib, self._lib.nutls_enhance_block_pcm_host(self._h, x.ctypes.data, o.ctypes.data, n, dc))
         return o
 
-    def pcm_decode_block_device(self, pcm, out=None):
+    def pcm_decode_block_device(self, pcm, out=None, hops=None):
         """The decode half on its own: ``[utterances, n_hops * pcm_hop_samples]`` of the handle's sample type -> ``[utterances, n_hops*256]``
-        float32 at 16 kHz (what ``enhance_block_device`` takes)."""
+        float32 at 16 kHz (what ``enhance_block_device`` takes).  ``hops``: per-utterance counts (``nutls_pcm_decode_block_ragged``)."""
         import torch
         S = self.pcm_hop_samples
         n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
         x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
         o = (torch.empty((self.utterances, n * 256), dtype=torch.float32, device=x.device) if out is None
              else self._pcm_tensor(out, self.utterances, n * 256, "out", torch.float32))
-        _check(self._lib, self._lib.nutls_pcm_decode_block(self._h, x.data_ptr(), o.data_ptr(), n, torch.cuda.current_stream(x.device).cuda_stream))
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if hops is None:
+            _check(self._lib, self._lib.nutls_pcm_decode_block(self._h, x.data_ptr(), o.data_ptr(), n, stream))
+        else:
+            _check(self._lib, self._lib.nutls_pcm_decode_block_ragged(self._h, x.data_ptr(), o.data_ptr(), n, self._device_counts(hops, n, x, "hops"), stream))
         return o
 
-    def pcm_encode_block_device(self, wave, out=None):
-        """The encode half on its own: ``[utterances, n_hops*256]`` float32 at 16 kHz -> the handle's format."""
+    def pcm_encode_block_device(self, wave, out=None, hops=None):
+        """The encode half on its own: ``[utterances, n_hops*256]`` float32 at 16 kHz -> the handle's format.  ``hops``: per-utterance counts
+        (``nutls_pcm_encode_block_ragged``)."""
         import torch
         S = self.pcm_hop_samples
         n = self._pcm_block_hops(int(wave.shape[-1]) if hasattr(wave, "shape") and len(wave.shape) == 2 else -1, 256, "wave")
         x = self._pcm_tensor(wave, self.utterances, n * 256, "wave", torch.float32)
         o = (torch.empty((self.utterances, n * S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None
              else self._pcm_tensor(out, self.utterances, n * S, "out"))
-        _check(self._lib, self._lib.nutls_pcm_encode_block(self._h, x.data_ptr(), o.data_ptr(), n, torch.cuda.current_stream(x.device).cuda_stream))
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if hops is None:
+            _check(self._lib, self._lib.nutls_pcm_encode_block(self._h, x.data_ptr(), o.data_ptr(), n, stream))
+        else:
+            _check(self._lib, self._lib.nutls_pcm_encode_block_ragged(self._h, x.data_ptr(), o.data_ptr(), n, self._device_counts(hops, n, x, "hops"), stream))
         return o
 
     def _wave_through_blocks(self, x: np.ndarray, lag: int, block) -> np.ndarray:
@@ -1091,17 +1113,19 @@ class NutlsOffline(_PcmFormat):
         return out if batched else out[0]
 
     # -- ragged blocks: per-utterance counts (nutls_process_block_ragged_host / nutls_enhance_block_ragged_host) ---------------------
-    def _ragged_host(self, entry, chunks, unit: int, *tail):
+    def _ragged_host(self, entry, chunks, unit: int, *tail, dtype=None):
         """One ragged block through a ``_host`` entry.  ``chunks[u]``: utterance u's piece of the block, ``k_u`` frames ``[k_u,256]``
-        (``unit`` 1) or ``k_u`` hops of PCM ``[k_u * 256]`` (``unit`` 256), k_u <= max_frames and at least one > 0; the row stride of the
-        block is the longest count.  Returns each utterance's piece of the result."""
+        (``unit`` 1) or ``k_u`` hops of PCM ``[k_u * unit]`` (``unit`` 256: float32 at 16 kHz), k_u <= max_frames and at least one > 0; the
+        row stride of the block is the longest count.  ``dtype``: the sample type of an entry that takes the callers' format (``unit`` =
+        ``pcm_hop_samples``, buffers handed over as addresses); None: float32.  Returns each utterance's piece of the result."""
         counts = np.array([c.shape[0] // unit for c in chunks], np.int32)
         n = int(counts.max())
-        blk = np.zeros((self.utterances, n * unit) + chunks[0].shape[1:], np.float32)
+        blk = np.zeros((self.utterances, n * unit) + chunks[0].shape[1:], dtype or np.float32)
         for u, c in enumerate(chunks):
             blk[u, :c.shape[0]] = c
         out = np.empty_like(blk)
-        _check(self._lib, entry(self._h, _fptr(blk), _fptr(out), n, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), *tail))
+        ptr = _fptr if dtype is None else (lambda a: a.ctypes.data)
+        _check(self._lib, entry(self._h, ptr(blk), ptr(out), n, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), *tail))
         return [out[u, :c.shape[0]] for u, c in enumerate(chunks)]
 
     def _ragged_list(self, items, what: str, ndim: int):
@@ -1138,12 +1162,17 @@ class NutlsOffline(_PcmFormat):
                 o[a * 256:a * 256 + len(g)] = g
         return [o[256:] for o in outs]
 
-    def enhance_many(self, waves, dc_mode: str = "edge") -> List[np.ndarray]:
+    def enhance_many(self, waves, dc_mode: str = "edge", rate: Optional[int] = None) -> List[np.ndarray]:
         """ANY NUMBER of recordings ``[N_i]`` of any lengths through the handle's ``utterances`` slots (:func:`plan_ragged_blocks`: longest
         first; a recording longer than one block continues in its slot, a slot whose recording has ended is reset and takes the next one of
         the queue in the next block, the other slots are not disturbed) -> the enhanced recordings in input order, each what
-        :meth:`enhance` of a fresh one-utterance handle returns for it.  Every slot that was used starts from a reset."""
+        :meth:`enhance` of a fresh one-utterance handle returns for it.  Every slot that was used starts from a reset.
+        ``rate`` (8000, 16000, 32000, 48000): the recordings are in the callers' format, int16 or float32 arrays at that rate, all of one
+        dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
+        handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format."""
         dc = self._dc(dc_mode)
+        if rate is not None:
+            return self._enhance_many_pcm(waves, dc, rate)
         waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
         if any(w.ndim != 1 for w in waves):
             raise ValueError("waves must be one-dimensional arrays")
@@ -1160,6 +1189,44 @@ class NutlsOffline(_PcmFormat):
             for slot, item, first, count, _ in block:
                 outs[item][first * 256:(first + count) * 256] = got[slot]
         return [o[256:] for o in outs]
+
+    _PCM_RATES = (8000, 16000, 32000, 48000)
+
+    def _enhance_many_pcm(self, waves, dc: int, rate) -> List[np.ndarray]:
+        """:meth:`enhance_many` in the callers' format.  Every recording is padded with zeros to whole hops that cover ``N + lag`` samples,
+        ``lag = pcm_hop_samples + pcm_delay_samples`` (the rule of :meth:`_wave_through_blocks`), and the lag is dropped from the front."""
+        waves = [np.asarray(w) for w in waves]
+        if any(w.ndim != 1 for w in waves):
+            raise ValueError("waves must be one-dimensional arrays")
+        names = {w.dtype.name for w in waves}
+        if len(names) > 1 or not names <= set(self._PCM_FORMATS):
+            raise ValueError("with a rate, waves must all be int16 or all be float32, got %s" % sorted(names))
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) not in self._PCM_RATES:
+            raise ValueError("rate must be 8000, 16000, 32000 or 48000, got %r" % (rate,))
+        if not waves:
+            return []
+        dtype = waves[0].dtype
+        self.set_pcm_format(int(rate), dtype)
+        S = self.pcm_hop_samples
+        lag = S + self.pcm_delay_samples
+        hops = [max(1, -(-(len(w) + lag) // S)) for w in waves]
+        padded = []
+        for w, n in zip(waves, hops):
+            p = np.zeros(n * S, dtype)
+            p[:len(w)] = w
+            padded.append(p)
+        outs = [np.empty_like(p) for p in padded]
+        empty = np.zeros(0, dtype)
+        for block in plan_ragged_blocks(hops, self.utterances, self.max_frames):
+            chunks = [empty] * self.utterances
+            for slot, item, first, count, reset_before in block:
+                if reset_before:
+                    self.reset_utterance(slot)
+                chunks[slot] = padded[item][first * S:(first + count) * S]
+            got = self._ragged_host(self._lib.nutls_enhance_block_pcm_ragged_host, chunks, S, dc, dtype=dtype)
+            for slot, item, first, count, _ in block:
+                outs[item][first * S:(first + count) * S] = got[slot]
+        return [o[lag:lag + len(w)] for o, w in zip(outs, waves)]
 
     def debug_get(self, name: str, shape) -> np.ndarray:
         """Debug tensors of the handle, ``[utterances] + shape``: "phasor_block" (``shape = (n_hops, 257, 2)`` of the last analysed block)."""
