@@ -198,7 +198,12 @@ class NutlsRef:
     def _mlp_gate(self, m, name):
         w1, w2 = self.w[name + ".w1"], self.w[name + ".w2"]
         hid = torch.relu(m @ w1.reshape(16, 64).t() + self.w[name + ".b1"])
-        return torch.sigmoid(hid @ w2.reshape(64, 16).t() + self.w[name + ".b2"])
+        gate = torch.sigmoid(hid @ w2.reshape(64, 16).t() + self.w[name + ".b2"])
+        if self.trace is not None:          # "<stage>.ta" / "<stage>.fa" [B,64] and their hidden layers "<stage>.ta_hid" / ".fa_hid" [B,16]
+            prefix, kind = name.rsplit("_", 1)
+            self.trace["%s.%s" % (prefix, kind)] = gate
+            self.trace["%s.%s_hid" % (prefix, kind)] = hid
+        return gate
 
     def _ctfa(self, x, e0, prefix):
         """ctfa_rt (proposed.py:162-196) + residual (converter_proposed.py:258-262).

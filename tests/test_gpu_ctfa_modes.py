@@ -1,7 +1,8 @@
 """GPU: the causal 32-frame CTFA (the offline / training model's attention, /root/reference/dnn_model/models/proposed.py:125-160,
 :143-147) in the STREAMING fused kernel -- a non-default mode (the reference's streaming graph feeds the frequency branch TA / 32,
 proposed.py:179-183 with T = 1; that stays the default).  Checked against oracle B in the same mode, against the offline
-handle in the same mode, on the one-stream plan and on the packed plans; history semantics (reset, mode switch)."""
+handle in the same mode, on the one-stream plan and on the packed plans; history semantics (reset, mode switch).  Trained weights and
+the float32 oracle here; tests/test_gpu_ctfa_families.py runs the mode on designed gate weights against the float64 oracle."""
 import os
 
 import numpy as np

@@ -44,12 +44,15 @@ class Ledger:
         assert np.isfinite(got).all(), "%s: %soutput of frame %d is not finite" % (self.what, prefix, frame)
         self.add("%soutput, frame %d" % (prefix, frame), LAST_OP, WF.scaled_rms(got, want) / WF.OUT_BOUND)
 
-    def states(self, eng, want, streams):
-        """all 130 states of every stream of ``eng``; ``streams[b]``: the base stream that stream b of the handle carries"""
+    def states(self, eng, want, streams, prefix="", only=None):
+        """all 130 states of every stream of ``eng``; ``streams[b]``: the base stream that stream b of the handle carries; ``only``: the
+        streams of the handle to look at (all otherwise)"""
         for name in WF.state_names():
             got = eng.state_get(name)
             for b, s in enumerate(streams):
-                self.add("state %s, stream %d" % (name, b), WF.state_consumer(name), WF.scaled_rms(got[b].reshape(-1), want[name][s].reshape(-1)) / WF.STATE_BOUND)
+                if only is None or b in only:
+                    self.add("%sstate %s, stream %d" % (prefix, name, b), WF.state_consumer(name),
+                             WF.scaled_rms(got[b].reshape(-1), want[name][s].reshape(-1)) / WF.STATE_BOUND)
 
     def close(self):
         for kind, labels in (("against the float64 oracle", [k for k in self.ratio if k not in self.device]), ("between device paths", sorted(self.device))):
@@ -135,7 +138,7 @@ def test_packed_plans_outputs_states_and_slot_independence(family, G):
 
 
 # ---- c. per-layer kernels ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("family", ["plain", "satbias", "const"])
+@pytest.mark.parametrize("family", ["plain", "satbias", "const", "gatesat", "gatedead", "gatehist"])
 def test_per_layer_kernels(family):
     """hipGraph replay and plain launches of the per-layer kernels on the shipped-form container: outputs and all 130 states of the four
     base streams against the float64 oracle, the two modes bit-identical to each other (as test_execution_modes_agree asserts)."""

@@ -1,6 +1,6 @@
 """Synthetic weight families, inputs and float64 reference values for the LSTM-variant kernels (a plain helper module: the CPU tests
-of tests/test_weight_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py and tests/test_gpu_conv_variants.py share it,
-and its caches) and, in its second
+of tests/test_weight_families.py and tests/test_ctfa_families.py and the GPU tests of tests/test_gpu_synthetic_weights.py,
+tests/test_gpu_conv_variants.py and tests/test_gpu_ctfa_families.py share it, and its caches) and, in its second
 half (``variant="baseline"``), for the dilated-dense baseline's (tests/test_baseline_families.py, tests/test_gpu_baseline_families.py).
 
 Every family starts from ``synthetic_weights("lstm", SEED, bias_std=0.1, affine_jitter=0.1)`` and is stored as the export stores the
@@ -48,7 +48,16 @@ SCALES_SEED = 41
 TINYVAR_CONVS = ("input_layer", "msfe5_en_conv2", "msfe4_de_spconv1", "msfe6_de_in", "msfe6_de_spconv6")
 TINYVAR_FACTOR = np.float32(3e-4)
 
-BASE_FAMILIES = ("plain", "satbias", "const", "dead", "scales", "alpha", "tinyvar")
+# The CTFA gate perceptrons (`*_ta` / `*_fa` .w1 .b1 .w2 .b2, 24 of them): `gatesat` puts SAT_PATTERN on every b2 (gates of exactly 0 and
+# 1), `gatedead` kills hidden layers, hidden units or output rows, `gatehist` makes the frequency branch answer strongly to its input, which
+# in the causal 32-frame mode is the mean of the last 32 time-attention vectors.
+# `gatehist` scales w1 of BOTH gates of every stage.  With the frequency gates alone the history hardly matters: every gate sits behind a
+# LayerNorm, so on plain weights the time attention of stream 1 of `causal_streams` moves by 0.003 between silence and a tone of 50, and the
+# frequency attention, 16 times as sensitive, by 0.043 between frame 32 and frame 64 (float64 oracle).  With the time gates scaled as well
+# it moves by 0.23 (tests/test_ctfa_families.py asserts more than 0.1); fa.w1 x 64 alone gives 0.12, fa.w1 x 16 with ta.w1 x 4 gives 0.12.
+GATEHIST_FACTOR = np.float32(16.0)
+GATE_FAMILIES = ("gatesat", "gatedead", "gatehist")
+BASE_FAMILIES = ("plain", "satbias", "const", "dead", "scales", "alpha", "tinyvar") + GATE_FAMILIES
 FORM_FAMILIES = tuple("forms_" + f for f in EXPORT_FORMS if f != "shipped")
 FAMILIES = BASE_FAMILIES + FORM_FAMILIES
 
@@ -156,9 +165,34 @@ def family_tensors(family, variant="lstm"):
         for layer in TINYVAR_CONVS:
             w[layer + ".w"] = (w[layer + ".w"] * TINYVAR_FACTOR).astype(np.float32)
             w[layer + ".b"] = np.zeros_like(w[layer + ".b"])
+    elif family == "gatesat":
+        # every gate of every stage has channels at +-100, +-30, +-8 and 0: __expf overflows to inf and the reciprocal gives exactly 0
+        for n, g in enumerate(gate_prefixes()):
+            w[g + ".b2"] = (w[g + ".b2"] + SAT_PATTERN[(np.arange(64) * 5 + n) % 7]).astype(np.float32)
+    elif family == "gatedead":
+        for n, g in enumerate(gate_prefixes()):
+            if n % 3 == 0:
+                w[g + ".b1"] = np.full_like(w[g + ".b1"], -10.0)          # hidden layer all zero after ReLU: the gate is sigmoid(b2)
+            elif n % 3 == 1:
+                w[g + ".w1"][::2] = 0.0          # every second hidden unit is relu(b1) whatever comes in
+            else:
+                w[g + ".w2"][::3] = 0.0          # every third gate channel is sigmoid(b2) whatever comes in
+    elif family == "gatehist":
+        for g in gate_prefixes():          # (both gates: see GATEHIST_FACTOR)
+            w[g + ".w1"] = (w[g + ".w1"] * GATEHIST_FACTOR).astype(np.float32)
     else:
         raise ValueError("unknown family %s" % family)
     return w
+
+
+def gate_prefixes():
+    """The 24 gate perceptrons, sorted: ``<stage>_fa`` and ``<stage>_ta`` of the 12 stages."""
+    return sorted("%s_%s" % (st.prefix, kind) for st in T.STAGES for kind in ("ta", "fa"))
+
+
+def gate_traced_names():
+    """The oracle's trace keys of the gates: ``<stage>.ta`` / ``.fa`` [B, 64] and their hidden layers ``.ta_hid`` / ``.fa_hid`` [B, 16]."""
+    return ["%s.%s%s" % (st.prefix, kind, hid) for st in T.STAGES for kind in ("ta", "fa") for hid in ("", "_hid")]
 
 
 @functools.lru_cache(maxsize=None)
@@ -213,6 +247,51 @@ def inputs(batch, variant="lstm", tail=False):
         x = baseline_streams()[BASE_FRAMES:] if tail else baseline_streams()[:BASE_FRAMES]
         return np.ascontiguousarray(x[:, np.arange(batch) % 4])
     return np.ascontiguousarray(base_streams()[:, np.arange(batch) % 4])
+
+
+# ---- the causal 32-frame CTFA (tests/test_ctfa_families.py, tests/test_gpu_ctfa_families.py) ------------------------------------------------
+# 70 frames: the streaming handle's history ring wraps at 32 and at 64 and the run ends at slot 6.  The onsets at 33 and 40 enter the
+# 32-frame window just after a wrap and fill it before the end.
+CAUSAL_FRAMES = 70
+CAUSAL_FAMILIES = ("plain", "gatesat", "gatedead", "gatehist")
+# the frames whose 18 traced tensors the causal references keep: the start, around the first frame with a full window (31), both wraps, the end
+CAUSAL_TRACE_FRAMES = (0, 1, 30, 31, 32, 33, 63, 64, 65, 69)
+# The offline block sets: (utterances = base streams, blocks, ragged calls [(block length, counts)]).  (17, 1, 31, 2, 19): the history is
+# rolled from a partly filled one, by one frame, by exactly 31; (33, 32, 5): blocks longer than the history; the ragged calls hold
+# utterance 1 (count 0) and then advance both by different counts.
+CAUSAL_BLOCKS = {2: ((0, 1), (17, 1, 31, 2, 19)), 1: ((3,), (33, 32, 5))}
+CAUSAL_RAGGED = ((17, (17, 0)), (20, (9, 20)))
+CAUSAL_RESTART = 40          # test c: `reset(1)` after this many frames
+CAUSAL_SWITCH = (10, 45)     # test c: frames in frame mode, then frames in causal32
+
+
+def causal_keep_frames():
+    """The frames after which the causal references keep all states: the end of every block of CAUSAL_BLOCKS, each utterance's own last
+    frame after each ragged call, and the last frame."""
+    keep = {CAUSAL_FRAMES - 1}
+    for _, blocks in CAUSAL_BLOCKS.values():
+        keep |= {sum(blocks[:i + 1]) - 1 for i in range(len(blocks))}
+    done = [0, 0]
+    for _, counts in CAUSAL_RAGGED:
+        done = [d + c for d, c in zip(done, counts)]
+        keep |= {d - 1 for d in done if d}
+    return frozenset(keep)
+
+
+@functools.lru_cache(maxsize=None)
+def causal_streams():
+    """[CAUSAL_FRAMES, 4, 256] float32: noise under a gain that swings between 0.02 and 1 from frame to frame; silence, then bin 40 at 50
+    from frame 33 on; steady noise; noise for 40 frames, then 1e-20 everywhere.  One generator per noise stream."""
+    n = CAUSAL_FRAMES
+    x = np.zeros((n, 4, 256), np.float32)
+    gain = np.float32(0.51 + 0.49 * np.cos(1.3 * np.arange(n)))
+    x[:, 0] = 0.25 * np.abs(np.random.default_rng([SEED + 7, 0]).standard_normal((n, 256))) * gain[:, None]
+    x[33:, 1, 40] = 50.0
+    x[:, 2] = 0.25 * np.abs(np.random.default_rng([SEED + 7, 2]).standard_normal((n, 256)))
+    x[:40, 3] = 0.25 * np.abs(np.random.default_rng([SEED + 7, 3]).standard_normal((40, 256)))
+    x[40:, 3] = 1e-20
+    x.setflags(write=False)
+    return x
 
 
 BLOCK_FRAMES = 27
@@ -287,35 +366,70 @@ class Run:
 
     def __init__(self, out, trace, state, states_at=None):
         self.out, self.trace, self.state, self.states_at = out, trace, state, states_at or {}
-        for a in [out] + list(trace.values()) + list(state.values()) + [a for d in self.states_at.values() for a in d.values()]:
+        traced = [a for v in trace.values() for a in (v.values() if isinstance(v, dict) else [v])]
+        for a in [out] + traced + list(state.values()) + [a for d in self.states_at.values() for a in d.values()]:
             a.setflags(write=False)
 
 
-def _oracle(blob, x, dtype, trace, variant="lstm", state=None, keep=()):
+def _oracle(blob, x, dtype, trace, variant="lstm", state=None, keep=(), ctfa_mode="frame", switch=None, trace_frames=None, gates=False,
+            oracle=NutlsRef):
     """x [frames, B, 256] through oracle B in ``dtype``; ``state``: the state tensors to start from (zeros otherwise); ``keep``: frame
-    indices after which all states are kept (``Run.states_at``)"""
-    ref = NutlsRef(parse_blob(blob), batch=x.shape[1], dtype=dtype, variant=variant)
+    indices after which all states are kept (``Run.states_at``).  ``ctfa_mode``: the oracle's; ``switch = (frame, mode)``: the mode is
+    changed in front of that frame, as ``nutls_set_ctfa_mode`` does it (the states carry over, the attention history starts empty).
+    ``trace_frames``: the frames whose 18 traced tensors are kept (``Run.trace[name]`` is then a dict frame -> tensor; None: every frame,
+    stacked); ``gates``: the gates and their hidden layers (`gate_traced_names`) of every frame too.  ``oracle``: the class (a mutant's)."""
+    ref = oracle(parse_blob(blob), batch=x.shape[1], dtype=dtype, variant=variant, ctfa_mode=ctfa_mode)
     if state is not None:
         for n in state_names(variant):
             assert ref.state[n].shape == state[n].shape, n
             ref.state[n] = torch.from_numpy(np.array(state[n])).to(dtype)
-    outs, tr = [], {n: [] for n in traced_names()} if trace else {}
+    outs, tr = [], {n: {} for n in traced_names()} if trace else {}
+    gt = {n: [] for n in gate_traced_names()} if gates else {}
     states_at = {}
     for f in range(x.shape[0]):
-        ref.trace = {} if trace else None
+        if switch is not None and f == switch[0]:
+            ref.ctfa_mode, ref.ta_hist = switch[1], {}
+        ref.trace = {} if trace or gates else None
         outs.append(ref.step(x[f]).numpy().astype(np.float64))
-        for n in tr:
-            tr[n].append(ref.trace[n].numpy().astype(np.float64))
+        if trace_frames is None or f in trace_frames:
+            for n in tr:
+                tr[n][f] = ref.trace[n].numpy().astype(np.float64)
+        for n in gt:
+            gt[n].append(ref.trace[n].numpy().astype(np.float64))
         if f in keep:
             states_at[f] = {n: ref.state[n].numpy().astype(np.float64) for n in state_names(variant)}
     state = {n: ref.state[n].numpy().astype(np.float64) for n in state_names(variant)}
-    return Run(np.stack(outs), {n: np.stack(v) for n, v in tr.items()}, state, states_at)
+    if trace_frames is None:
+        tr = {n: np.stack([v[f] for f in range(x.shape[0])]) for n, v in tr.items()}
+    tr.update({n: np.stack(v) for n, v in gt.items()})
+    return Run(np.stack(outs), tr, state, states_at)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(family, dtype=torch.float64, form=None, variant="lstm"):
-    """The four base streams through the oracle on the family's container (computed once per process, never modified)."""
+def reference(family, dtype=torch.float64, form=None, variant="lstm", ctfa_mode="frame", frames="base"):
+    """The four base streams through the oracle on the family's container (computed once per process, never modified).
+    ``ctfa_mode="causal32"`` or ``frames="causal"``: the CAUSAL_FRAMES frames of `causal_streams` instead, the 18 traced tensors of
+    CAUSAL_TRACE_FRAMES, the gates of every frame, and all states after the frames of `causal_keep_frames`."""
+    if ctfa_mode == "causal32" or frames == "causal":
+        if variant != "lstm":
+            raise ValueError("the causal inputs are the LSTM variant's")
+        return _oracle(container(family, form), causal_streams(), dtype, trace=True, keep=causal_keep_frames(), ctfa_mode=ctfa_mode,
+                       trace_frames=frozenset(CAUSAL_TRACE_FRAMES), gates=True)
     return _oracle(container(family, form, variant), inputs(4, variant), dtype, trace=True, variant=variant)
+
+
+@functools.lru_cache(maxsize=None)
+def causal_restart_reference(family):
+    """Base stream 1 of `causal_streams` from frame CAUSAL_RESTART on through a float64 oracle that starts from nothing, causal32."""
+    return _oracle(container(family), np.ascontiguousarray(causal_streams()[CAUSAL_RESTART:, 1:2]), torch.float64, trace=False, ctfa_mode="causal32")
+
+
+@functools.lru_cache(maxsize=None)
+def causal_switch_reference(family):
+    """Base streams 0 and 1: CAUSAL_SWITCH[0] frames in frame mode, then CAUSAL_SWITCH[1] frames in causal32 (float64)."""
+    n0, n1 = CAUSAL_SWITCH
+    return _oracle(container(family), np.ascontiguousarray(causal_streams()[:n0 + n1, :2]), torch.float64, trace=False, ctfa_mode="frame",
+                   switch=(n0, "causal32"))
 
 
 @functools.lru_cache(maxsize=None)
