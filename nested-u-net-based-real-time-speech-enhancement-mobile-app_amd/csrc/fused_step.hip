@@ -233,7 +233,18 @@ __device__ __forceinline__ f32x4& lds4s(int boff) { return *reinterpret_cast<f32
 __device__ __forceinline__ float& lds1s(int boff) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + boff); }
 // workgroup barrier that orders LDS traffic only (global loads / stores stay in flight across it)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// (one-stream plans: the wait as the compiler's own instruction between two memory fences, so that its wait-count pass KNOWS the counter is zero
+//  behind it.  A register whose load only some waves wait for -- the consumer sits in a wave-role block -- is still "pending" for it at the join; where
+//  such a register was re-used right behind an inline-asm drain it put a second, useless `s_waitcnt vmcnt(n)` behind the `vmcnt(0)`.)
+__device__ __forceinline__ void drain_vm() {
+  if constexpr (kStreams == 1) {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt and lgkmcnt left alone (gfx9 encoding: vmcnt in bits 3:0 and 15:14)
+    asm volatile("" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
 
 template <class F, int... Is>
 __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
@@ -248,6 +259,63 @@ __device__ __forceinline__ void sched_pin() { __builtin_amdgcn_sched_barrier(0);
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int cmin(int a, int b) { return a < b ? a : b; }
 constexpr int clog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+// ---- wave roles (one-stream plans) --------------------------------------------------------------------------------------
+// Which threads take part in a block of an op (`tid < 129`, the staging slots dealt from the top, the halo threads from wave 4 ...) is a
+// fact of the plan, and so is which of the 8 WAVES do.  Guarded by a lane predicate alone, every wave issues v_cmp + s_and_saveexec +
+// s_cbranch_execz (+ s_or exec) for every block of every op, the waves that have no lane in it included -- on the critical wave of a small
+// op that was 20 of its 220 instructions.  role_block guards the block with a compare of the scalar wave index (s_cmp + s_cbranch_scc)
+// and keeps the lane predicate only where a boundary wave is partial.  (FZ_WAVE_ROLES: developer switch of the A/B builds.)
+#ifndef FZ_WAVE_ROLES
+#define FZ_WAVE_ROLES 1
+#endif
+constexpr bool FZ_ROLES = FZ_PINNED_FORMS && FZ_WAVE_ROLES != 0;
+constexpr int WAVES = THREADS / 64;
+struct Waves { int first, last; bool partial; };      // waves first .. last hold the block's threads (first > last: none); partial: a boundary wave holds other threads too
+constexpr Waves waves_span(int lo, int hi) {          // threads lo <= tid < hi, clipped to the workgroup: `(unsigned)(tid - lo) < hi - lo`
+  const int l = lo < 0 ? 0 : lo, h = hi > THREADS ? THREADS : hi;
+  return h <= l ? Waves{1, 0, false} : Waves{l / 64, (h - 1) / 64, l % 64 != 0 || h % 64 != 0};
+}
+constexpr Waves waves_lt(int n) { return waves_span(0, n); }                      // tid < n
+constexpr Waves waves_ge(int n) { return waves_span(n, THREADS); }                // tid >= n
+constexpr Waves waves_top(int n) { return waves_span(THREADS - n, THREADS); }     // THREADS - 1 - tid < n: items dealt from the top of the workgroup
+// staging slots dealt from the top (stage_slot): the threads whose slot is below `rem` -- among nthr staging threads, the first of them
+// thread `off` of the workgroup, the deal shifted by `shift` -- are off + [nthr - shift - rem, nthr - shift); a negative start: the span wraps
+// around the staging threads (slots_wrap: the lane predicate alone decides, as it did)
+constexpr int slots_lo(int rem, int shift, int nthr, int off) { return off + nthr - shift - rem; }
+constexpr int slots_hi(int shift, int nthr, int off) { return off + nthr - shift; }
+constexpr bool slots_wrap(int rem, int shift, int nthr) { return nthr - shift - rem < 0; }
+__device__ __forceinline__ int wave_of(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
+// (pred: the lane predicate that says `LO <= tid < HI`; LIKELY: the branch hint the predicate carried before)
+template <int LO, int HI, bool LIKELY = true, class F>
+__device__ __forceinline__ void role_block(int wave, bool pred, F&& body) {
+  constexpr Waves w = waves_span(LO, HI);
+  auto lanes = [&] {
+    if constexpr (LIKELY) { if (__builtin_expect(pred, 1)) body(); }
+    else { if (pred) body(); }
+  };
+  if constexpr (w.first == 0 && w.last == WAVES - 1 && !w.partial) {
+    body();
+  } else if constexpr (!FZ_ROLES) {
+    lanes();
+  } else if constexpr (w.first <= w.last) {
+    bool in = true;
+    if constexpr (w.first > 0 && w.last < WAVES - 1) in = static_cast<unsigned>(wave - w.first) <= static_cast<unsigned>(w.last - w.first);
+    else if constexpr (w.first > 0) in = wave >= w.first;
+    else if constexpr (w.last < WAVES - 1) in = wave <= w.last;
+    if (in) {
+      if constexpr (w.partial) lanes();
+      else body();
+    }
+  }
+}
+
+// row x pitch of an LDS buffer: both far below 2^24, so the 24-bit multiply is exact -- one full-rate v_mul_u32_u24 with the pitch as its literal
+// where `row * pitch` in 32 bits is a quarter-rate v_mul_lo_u32 plus the s_movk that holds the pitch (one-stream plans; the packed kernels keep `*`)
+__device__ __forceinline__ int row_x_pitch(int row, int pitch_b) {
+  if constexpr (FZ_PINNED_FORMS) return __umul24(static_cast<unsigned>(row), static_cast<unsigned>(pitch_b));
+  else return row * pitch_b;
+}
+
 constexpr int img_row_b(int pitch_b, int pair, int half_b, int lr) { return pair ? (lr >> 1) * pitch_b + (lr & 1) * half_b : lr * pitch_b; }
 __device__ __forceinline__ int img_row_rt(int pitch_b, int pair, int half_b, int lr) { return pair ? (lr >> 1) * pitch_b + (lr & 1) * half_b : lr * pitch_b; }
 
@@ -513,8 +581,22 @@ __device__ __forceinline__ void stage_load(const Ctx& cx, int tid, f32x4 (&r)[NR
     });
   }
 }
+// first wave of the workgroup that stores an item of image J's parts of class CLS (WAVES: none does); the NTHR staging threads are the TOP ones
+constexpr int stage_first_wave(int j, int cls, int nthr) {
+  int w = WAVES;
+  if (j < 0 || j >= kNumOps) return w;
+  const Img& g = kOps[j].img;
+  for (int k = 0; k < g.nparts; ++k) {
+    if (part_cls(g.parts[k]) != cls) continue;
+    const int items = part_items(g.parts[k]), sh = part_shift(g, cls, k, nthr), rem = items % nthr, off = THREADS - nthr;
+    if (items >= nthr || slots_wrap(rem, sh, nthr)) w = cmin(w, off / 64);
+    else if (rem > 0) w = cmin(w, slots_lo(rem, sh, nthr, off) / 64);
+  }
+  return w;
+}
+// (tid: index among the NTHR staging threads, the top ones of the workgroup; wave: the thread's wave in the workgroup)
 template <int J, int CLS, int NTHR, int NR>
-__device__ __forceinline__ void stage_store(int tid, const f32x4 (&r)[NR]) {
+__device__ __forceinline__ void stage_store(int tid, int wave, const f32x4 (&r)[NR]) {
   if constexpr (J >= 0 && J < kNumOps) {
     constexpr Img g = kOps[J].img;
     sfor<g.nparts>([&](auto kk) {
@@ -522,14 +604,20 @@ __device__ __forceinline__ void stage_store(int tid, const f32x4 (&r)[NR]) {
       constexpr Part p = g.parts[K];
       if constexpr (part_cls(p) == CLS) {
         constexpr int items = part_items(p), per = p.rows * p.c4s, base = part_base(g, CLS, K, NTHR), cs = clog2(p.c4s), NG = p.ng;
-        const int slot = stage_slot<NTHR>(tid, part_shift(g, CLS, K, NTHR));
+        constexpr int SH = part_shift(g, CLS, K, NTHR);
+        const int slot = stage_slot<NTHR>(tid, SH);
         sfor<part_n(p, NTHR)>([&](auto ii) {
           constexpr int i = decltype(ii)::value;
           const int q = slot + NTHR * i;
           const int gi = NG > 1 ? q >> clog2(per) : 0, ql = NG > 1 ? q & (per - 1) : q;
           const int row = ql >> cs, c4 = ql & (p.c4s - 1);
           const int a = p.lds_b + gi * p.gstride_b + img_row_rt(g.pitch_b, g.pair, g.half_b, p.row0 + row) + c4 * (4 * esz_of(g.fmt));
-          if ((i + 1) * NTHR <= items || FZ_LIKELY(q < items)) img_st4<g.fmt>(a, g.plane_b, r[base + i]);
+          constexpr int rem = items - NTHR * i;      // items of this pass when it is the last, partial one
+          if constexpr (!FZ_ROLES || (i + 1) * NTHR <= items || slots_wrap(rem, SH, NTHR)) {
+            if ((i + 1) * NTHR <= items || FZ_LIKELY(q < items)) img_st4<g.fmt>(a, g.plane_b, r[base + i]);
+          } else {
+            role_block<slots_lo(rem, SH, NTHR, THREADS - NTHR), slots_hi(SH, NTHR, THREADS - NTHR)>(wave, q < items, [&] { img_st4<g.fmt>(a, g.plane_b, r[base + i]); });
+          }
         });
       }
     });
@@ -541,12 +629,29 @@ __device__ __forceinline__ void stage_store(int tid, const f32x4 (&r)[NR]) {
 constexpr int zero_total(const Img& g) { int n = 0; for (int k = 0; k < g.nzero; ++k) n += g.zero[k].n4; return n; }
 constexpr int zero_first(const Img& g) { return cmin(THREADS / 2, THREADS - zero_total(g)); }
 constexpr int zero_start(const Img& g, int k) { int n = zero_first(g); for (int kk = 0; kk < k; ++kk) n += g.zero[kk].n4; return n; }
+constexpr bool zero_wave_aligned(const Img& g) { for (int k = 1; k < g.nzero; ++k) if (zero_start(g, k) % 64 != 0) return false; return true; }
+constexpr int zero_first_wave(int j) { return (j >= 0 && j < kNumOps && kOps[j].img.nzero > 0) ? zero_first(kOps[j].img) / 64 : WAVES; }
 template <int J>
-__device__ __forceinline__ void zero_halos(int tid) {
+__device__ __forceinline__ void zero_halos(int tid, int wave) {
   if constexpr (J >= 0 && J < kNumOps) {
     constexpr Img g = kOps[J].img;
     static_assert(zero_total(g) <= THREADS, "halo blocks: one float4 per thread");
-    if constexpr (g.nzero > 0) {
+    if constexpr (g.nzero > 0 && FZ_ROLES) {
+      role_block<zero_first(g), zero_first(g) + zero_total(g)>(wave, static_cast<unsigned>(tid - zero_first(g)) < static_cast<unsigned>(zero_total(g)), [&] {
+        // (everything the block needs is made inside it: a wave without a halo thread issues the one scalar test)
+        int delta = g.zero[0].lds_b - zero_start(g, 0) * 16;        // LDS address of thread t's float4 = delta + 16 t
+        sfor<g.nzero - 1>([&](auto kk) {
+          constexpr int K = decltype(kk)::value + 1;
+          // (blocks that start at a wave: the block of a thread is the block of its wave -- scalar selects, no v_cmp / v_cndmask chain and its hazard nops)
+          if constexpr (zero_wave_aligned(g)) delta = wave >= zero_start(g, K) / 64 ? g.zero[K].lds_b - zero_start(g, K) * 16 : delta;
+          else delta = tid >= zero_start(g, K) ? g.zero[K].lds_b - zero_start(g, K) * 16 : delta;
+        });
+        unsigned long long z0 = 0ull, z1 = 0ull;
+        asm volatile("" : "+v"(z0), "+v"(z1));
+        const u64x2 zq = {z0, z1};
+        lds4(delta + tid * 16) = __builtin_bit_cast(f32x4, zq);
+      });
+    } else if constexpr (g.nzero > 0) {
       int delta = g.zero[0].lds_b - zero_start(g, 0) * 16;        // LDS address of thread t's float4 = delta + 16 t
       sfor<g.nzero - 1>([&](auto kk) {
         constexpr int K = decltype(kk)::value + 1;
@@ -806,27 +911,46 @@ __device__ __forceinline__ void ext_load(const Ctx& cx, int tid, f32x4 (&wx)[NX]
 }
 
 // ---- completing the next image: staged parts + halos (between the two barriers of op I) --------------------------
+// first wave that has anything to do in build_next<I> (WAVES: none)
+constexpr int build_first_wave(int i) {
+  return cmin(cmin(stage_first_wave(nxt_of(i), 1, stg_threads(i)), stage_first_wave(nxt_of(i), 2, THREADS)), zero_first_wave(nxt_of(i)));
+}
 template <int I, int N1, int N2>
-__device__ __forceinline__ void build_next(int tid, const f32x4 (&p1)[N1], const f32x4 (&p2)[N2]) {
+__device__ __forceinline__ void build_next(int tid, int wave, const f32x4 (&p1)[N1], const f32x4 (&p2)[N2]) {
   constexpr int J = nxt_of(I), ST = stg_threads(I);
   if constexpr (ST == THREADS) {
-    stage_store<J, 1, THREADS>(tid, p1);
+    stage_store<J, 1, THREADS>(tid, wave, p1);
   } else {
-    if (__builtin_amdgcn_readfirstlane(tid >> 6) >= (THREADS - ST) / 64) stage_store<J, 1, ST>(tid - (THREADS - ST), p1);
+    if (wave >= (THREADS - ST) / 64) stage_store<J, 1, ST>(tid - (THREADS - ST), wave, p1);
   }
-  stage_store<J, 2, THREADS>(tid, p2);
-  zero_halos<J>(tid);
+  stage_store<J, 2, THREADS>(tid, wave, p2);
+  zero_halos<J>(tid, wave);
+}
+// Between the two barriers of a conv op, behind the epilogue rows: the carried sums (`sums`), the staged parts and the halos belong to the
+// upper waves; a wave whose only role was the epilogue reaches the closing barrier behind ONE scalar test.
+template <int I, int SUMS_FIRST, int N1, int N2, class F>
+__device__ __forceinline__ void finish_op(int tid, int wave, const f32x4 (&p1)[N1], const f32x4 (&p2)[N2], F&& sums) {
+  constexpr int FIRST = cmin(SUMS_FIRST, build_first_wave(I));
+  if constexpr (!FZ_ROLES || FIRST == 0) {
+    sums();
+    build_next<I>(tid, wave, p1, p2);
+  } else if constexpr (FIRST < WAVES) {
+    if (wave >= FIRST) {
+      sums();
+      build_next<I>(tid, wave, p1, p2);
+    }
+  }
 }
 // the second-round part of an op's own two-round image (between the two barriers in the middle of the op)
 template <int I, int N3, int N4>
-__device__ __forceinline__ void store_round2(int tid, const f32x4 (&p3)[N3], const f32x4 (&p4)[N4]) {
+__device__ __forceinline__ void store_round2(int tid, int wave, const f32x4 (&p3)[N3], const f32x4 (&p4)[N4]) {
   constexpr int ST = stg_threads(I);
   if constexpr (ST == THREADS) {
-    stage_store<I, 3, THREADS>(tid, p3);
+    stage_store<I, 3, THREADS>(tid, wave, p3);
   } else {
-    if (__builtin_amdgcn_readfirstlane(tid >> 6) >= (THREADS - ST) / 64) stage_store<I, 3, ST>(tid - (THREADS - ST), p3);
+    if (wave >= (THREADS - ST) / 64) stage_store<I, 3, ST>(tid - (THREADS - ST), wave, p3);
   }
-  stage_store<I, 4, THREADS>(tid, p4);
+  stage_store<I, 4, THREADS>(tid, wave, p4);
 }
 
 // LDS address of (output row `row`, channel c) inside the forward target of op I (hi plane of a three-plane image)
@@ -862,7 +986,7 @@ constexpr bool feeds_x(int i) { return i + 1 < kNumOps && (kOps[i + 1].type == T
 // ---- row-wise epilogue of the X16B path ---------------------------------------------------------------------------
 // LPG lanes per output row (float4 each): K-slice sum + bias, LayerNorm over the row's channels, PReLU, stores.
 template <int I, int NTHR = THREADS, int NY>
-__device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (&yp)[NY]) {
+__device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, int wave, const f32x4 (&yp)[NY]) {
   constexpr OpD d = kOps[I];
   // (two-tap convs: slices [0, KS) of the exchange buffer hold the NEXT frame's partial sums, [KS, 2 KS) this frame's)
   constexpr int GC = d.gc, LPG = GC / 4, R = d.R, NTOT = ntot(d), KS = ex_group(d), K0 = d.ys ? KS : 0, OPB = (NTOT + 4) * 4;
@@ -886,10 +1010,11 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
   sfor<passes>([&](auto pp) {
     constexpr int ps = decltype(pp)::value;
     const int u = u0 + ps * (NTHR / LPG);
-    if ((ps + 1) * NTHR <= total || FZ_LIKELY(u * LPG < total)) {
+    // (whole rows of LPG lanes: `u LPG < total` is `tid < total - ps NTHR`)
+    role_block<0, (ps + 1) * NTHR <= total ? THREADS : total - ps * NTHR>(wave, u * LPG < total, [&] {
       const int vpos = u >> clog2(R);
       const int gi = d.gs > 1 ? vpos >> clog2(d.P) : 0, pos = d.gs > 1 ? vpos & (d.P - 1) : vpos;      // stream slot, position inside the stream
-      const int eb = d.ex_b + vpos * OPB + (r * GC + 4 * li) * 4;
+      const int eb = d.ex_b + row_x_pitch(vpos, OPB) + (r * GC + 4 * li) * 4;
       // (from the first slice, not from zero: `0 + x` is an instruction the compiler may not drop -- it differs from x for x = -0 -- and the sums
       //  are the same bit for bit: an accumulator that starts at +0 never holds -0, so no slice does)
       f32x4 v = lds4(eb + K0 * (VP * OPB));
@@ -920,7 +1045,7 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
       sched_pin();
       if constexpr (d.d0_on) { if (FZ_D0(d, cx)) st_state<d.nt0 != 0>(d.d0_src == S_CUR ? cx.sbc : cx.sbs, static_cast<unsigned>((d.d0_off + row * d.d0_ld + 4 * li) * 4) + go, v); }
       if constexpr (d.d1_on) { if (FZ_D1(d, cx)) st_state<d.nt1 != 0>(d.d1_src == S_CUR ? cx.sbc : cx.sbs, static_cast<unsigned>((d.d1_off + row * d.d1_ld + 4 * li) * 4) + go, v); }
-    }
+    });
   });
   if constexpr (CSUM) {
     static_assert(LPG == 16 && NTHR == THREADS, "column sums: 16 lanes per row of 64 channels, all eight waves leave a partial row");
@@ -928,19 +1053,31 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
     for (int e = 0; e < 4; ++e) cs[e] = xor32_sum(xor16_sum(cs[e]));
     if ((tid & 63) < 16) lds4(kOps[I + 1].scr_b + CSUM_OFF_B + ((tid >> 6) * 64 + 4 * li) * 4) = cs;
   }
+}
+// The next frame's partial sums of a two-tap conv, W[tap 0] x_t: K slices summed, stored raw ([pos][packed channel] = item order) as float4
+// items dealt from the TOP of the workgroup, beside the epilogue rows of the low waves (both epilogue forms: the rows' lane layout does not matter here)
+constexpr int x_sums_items(const OpD& d) { return d.gs * d.P * ntot(d) / 4; }
+constexpr int x_sums_first_wave(int i) {
+  if (i < 0 || i >= kNumOps || kOps[i].type != T_CONV || kOps[i].path != P_X16B || !kOps[i].ys) return WAVES;
+  return cmax(0, THREADS - x_sums_items(kOps[i])) / 64;
+}
+template <int I>
+__device__ __forceinline__ void x_sums(const Ctx& cx, int tid, int wave) {
+  constexpr OpD d = kOps[I];
   if constexpr (d.ys != 0) {
-    // next frame's partial sums W[tap 0] x_t: K slices summed, stored raw ([pos][packed channel] = item order); the items are dealt
-    // from the top of the workgroup, beside the epilogue rows of the low waves
+    constexpr int GC = d.gc, LPG = GC / 4, R = d.R, NTOT = ntot(d), KS = ex_group(d), OPB = (NTOT + 4) * 4, VP = d.gs * d.P;
+    constexpr int total = x_sums_items(d), passes = (total + THREADS - 1) / THREADS;
+    static_assert(d.epl != 1 || passes == 1, "epl 1: at most one output element per thread");
     sfor<passes>([&](auto pp) {
       constexpr int ps = decltype(pp)::value;
-      const int item = (NTHR - 1 - tid) + ps * NTHR;
-      if ((ps + 1) * NTHR <= total || FZ_LIKELY(item < total)) {
+      const int item = (THREADS - 1 - tid) + ps * THREADS;
+      role_block<(ps + 1) * THREADS <= total ? 0 : (ps + 1) * THREADS - total, THREADS>(wave, item < total, [&] {
         const int u = item >> clog2(LPG), l2 = item & (LPG - 1);
-        const int eb = d.ex_b + (u >> clog2(R)) * OPB + ((u & (R - 1)) * GC + 4 * l2) * 4;
+        const int eb = d.ex_b + row_x_pitch(u >> clog2(R), OPB) + ((u & (R - 1)) * GC + 4 * l2) * 4;
         f32x4 y = lds4(eb);
         sfor<KS - 1>([&](auto kk) { y += lds4(eb + (decltype(kk)::value + 1) * (VP * OPB)); });
         st_next(cx.ysw, x16_ys_off<I>(cx, item), y);
-      }
+      });
     });
   }
 }
@@ -950,7 +1087,7 @@ __device__ __forceinline__ void x_epilogue(const Ctx& cx, int tid, const f32x4 (
 // three-plane split are ~50 dependent VALU instructions on EVERY wave that holds a row instead of ~110 on the one or two waves that hold
 // all rows as float4 -- this chain is the critical path of a small op (profiles/r05_v0_wave_trace.txt: 1 000 of its 2 800 cycles).
 template <int I, int NY>
-__device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 (&yp)[NY]) {
+__device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, int wave, const f32x4 (&yp)[NY]) {
   constexpr OpD d = kOps[I];
   constexpr int GC = d.gc, R = d.R, NTOT = ntot(d), KS = ex_group(d), K0 = d.ys ? KS : 0, OPB = (NTOT + 4) * 4;
   constexpr int VP = d.gs * d.P, total = VP * NTOT;
@@ -960,7 +1097,7 @@ __device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 
   const int u = tid >> clog2(GC);                 // output row: virtual position x sub-row
   const int r = u & (R - 1);
   constexpr bool CSUM = feeds_ctfa_sums(I);
-  if (total == THREADS || FZ_LIKELY(tid < total)) {
+  role_block<0, total>(wave, tid < total, [&] {
     const float bias = lds1(SCR_B + (r * GC + cch) * 4), wsc = lds1(SCR_B + (NTOT + r * GC + cch) * 4);
     float gm = 0.f, bt = 0.f, alpha = 0.f;
     if constexpr (d.ln) {
@@ -970,7 +1107,7 @@ __device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 
     }
     const int vpos = u >> clog2(R);
     const int gi = d.gs > 1 ? vpos >> clog2(d.P) : 0, pos = d.gs > 1 ? vpos & (d.P - 1) : vpos;
-    const int eb = d.ex_b + vpos * OPB + (r * GC + cch) * 4;
+    const int eb = d.ex_b + row_x_pitch(vpos, OPB) + (r * GC + cch) * 4;
     float v = lds1(eb + K0 * (VP * OPB));      // (from the first slice: see x_epilogue)
     sfor<KS - 1>([&](auto kk) { v += lds1(eb + (K0 + decltype(kk)::value + 1) * (VP * OPB)); });
     if constexpr (d.ys != 0) v += yp[0][0];      // W[tap 0] x_{t-1}, computed by this op one frame ago
@@ -992,19 +1129,7 @@ __device__ __forceinline__ void x_epilogue1(const Ctx& cx, int tid, const f32x4 
     sched_pin();
     if constexpr (d.d0_on) { if (FZ_D0(d, cx)) st_state1<d.nt0 != 0>(d.d0_src == S_CUR ? cx.sbc : cx.sbs, static_cast<unsigned>((d.d0_off + row * d.d0_ld + cch) * 4) + go, v); }
     if constexpr (d.d1_on) { if (FZ_D1(d, cx)) st_state1<d.nt1 != 0>(d.d1_src == S_CUR ? cx.sbc : cx.sbs, static_cast<unsigned>((d.d1_off + row * d.d1_ld + cch) * 4) + go, v); }
-  }
-  if constexpr (d.ys != 0) {
-    // next frame's partial sums W[tap 0] x_t: K slices summed, stored raw ([pos][packed channel]) as float4 items dealt from the top of the workgroup
-    constexpr int items = total / 4, LPG4 = GC / 4;
-    const int item = THREADS - 1 - tid;
-    if (FZ_LIKELY(item < items)) {
-      const int uu = item >> clog2(LPG4), l2 = item & (LPG4 - 1);
-      const int eb = d.ex_b + (uu >> clog2(R)) * OPB + ((uu & (R - 1)) * GC + 4 * l2) * 4;
-      f32x4 y = lds4(eb);
-      sfor<KS - 1>([&](auto kk) { y += lds4(eb + (decltype(kk)::value + 1) * (VP * OPB)); });
-      st_next(cx.ysw, x16_ys_off<I>(cx, item), y);
-    }
-  }
+  });
 }
 
 // ---- conv op, small layers: 16x16x32 bf16 tiles, K split over waves, LDS exchange -------------------------------------
@@ -1077,7 +1202,7 @@ __device__ __forceinline__ void conv_x16b(const Ctx& cx, int tid, Carry<I>& c, c
     static_assert(NF % 2 == 0, "two rounds: the same number of fragments per round");
     half(std::integral_constant<int, 0>{}, std::integral_constant<int, NF / 2>{});
     lds_barrier();
-    store_round2<I>(tid, p3, c.p4);
+    store_round2<I>(tid, wave, p3, c.p4);
     lds_barrier();
     half(std::integral_constant<int, NF / 2>{}, std::integral_constant<int, NF>{});
   } else {
@@ -1098,15 +1223,15 @@ __device__ __forceinline__ void conv_x16b(const Ctx& cx, int tid, Carry<I>& c, c
       }
     }
   }
-  if constexpr (prm_dword(d)) { if (FZ_LIKELY(tid < nparams(d))) lds1(SCR_B + tid * 4) = c.prm[0]; }
-  else { if (FZ_LIKELY(tid < (nparams(d) + 3) / 4)) lds4(SCR_B + tid * 16) = c.prm; }
+  if constexpr (prm_dword(d)) role_block<0, nparams(d)>(wave, tid < nparams(d), [&] { lds1(SCR_B + tid * 4) = c.prm[0]; });
+  else role_block<0, (nparams(d) + 3) / 4>(wave, tid < (nparams(d) + 3) / 4, [&] { lds4(SCR_B + tid * 16) = c.prm; });
   FZ_STAMP(I, 1);
   lds_barrier();
   FZ_STAMP(I, 2);
-  if constexpr (d.epl == 1) x_epilogue1<I>(cx, tid, c.yp);
-  else x_epilogue<I>(cx, tid, c.yp);
+  if constexpr (d.epl == 1) x_epilogue1<I>(cx, tid, wave, c.yp);
+  else x_epilogue<I>(cx, tid, wave, c.yp);
   FZ_STAMP(I, 3);
-  build_next<I>(tid, p1, c.p);
+  finish_op<I, x_sums_first_wave(I)>(tid, wave, p1, c.p, [&] { x_sums<I>(cx, tid, wave); });
   FZ_STAMP(I, 4);
 }
 
@@ -1185,7 +1310,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
     static_assert(NF % 2 == 0, "two rounds: the same number of fragments per round");
     half(std::integral_constant<int, 0>{}, std::integral_constant<int, NF / 2>{});
     lds_barrier();
-    store_round2<I>(tid, p3, c.p4);
+    store_round2<I>(tid, wave, p3, c.p4);
     lds_barrier();
     half(std::integral_constant<int, NF / 2>{}, std::integral_constant<int, NF>{});
   } else {
@@ -1215,8 +1340,8 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
             for (int e = 0; e < 4; ++e) acc[pt][n][4 * q + e] += c.yp[(pt * NT + n) * 4 + q][e];
     }
   }
-  if constexpr (prm_dword(d)) { if (FZ_LIKELY(tid < nparams(d))) lds1s(SCR_B + tid * 4) = c.prm[0]; }
-  else { if (FZ_LIKELY(tid < (nparams(d) + 3) / 4)) lds4s(SCR_B + tid * 16) = c.prm; }
+  if constexpr (prm_dword(d)) role_block<0, nparams(d)>(wave, tid < nparams(d), [&] { lds1s(SCR_B + tid * 4) = c.prm[0]; });
+  else role_block<0, (nparams(d) + 3) / 4>(wave, tid < (nparams(d) + 3) / 4, [&] { lds4s(SCR_B + tid * 16) = c.prm; });
   FZ_STAMP(I, 1);
   lds_barrier();                      // every wave is done with this op's image; parameters are in LDS
   FZ_STAMP(I, 2);
@@ -1292,7 +1417,7 @@ __device__ __forceinline__ void conv_r32b(const Ctx& cx, int tid, Carry<I>& c, c
     }
   }
   FZ_STAMP(I, 3);
-  build_next<I>(tid, p1, c.p);
+  finish_op<I, WAVES>(tid, wave, p1, c.p, [] {});
   FZ_STAMP(I, 4);
 }
 
@@ -1356,8 +1481,10 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
   constexpr int KN = lstm_kn(d.din), XS = clog2(d.x_cols), S0 = lstm_s0(d), GS = d.gs;
   constexpr int PART = d.scr_b, HN = d.scr_b + 20 * 21 * 16, SGB = d.scr_gstride_b;      // stream slot gi: + gi * SGB
   constexpr bool DI8 = lstm_dense_i8(d.dout);
-  const int u = tid % 21, sl = tid / 21;
+  const int u = tid % 21, sl = tid / 21, wave = wave_of(tid);
   pin_regs(c.w);
+  // (threads 0 .. 419 = waves 0 .. 6: the x slices end and the h slices begin inside wave 5, so those waves keep both lane predicates)
+  role_block<0, 448>(wave, true, [&] {
   if (tid < 336) {
     f32x4 a[GS];
 #pragma unroll
@@ -1384,6 +1511,7 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
       lds4(PART + gi * SGB + (sl * 21 + u) * 16) = a;
     }
   }
+  });
   FZ_WSTAMP(I, 3);
   lds_barrier();
   FZ_WSTAMP(I, 4);
@@ -1405,7 +1533,7 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
   }
 #pragma unroll
   for (int k = 0; k < 21; ++k) asm volatile("" : "+v"(wd[k]));
-  if (tid < 21 * GS) {          // thread (stream slot gi, unit uu): the unit's four gates
+  role_block<0, 21 * GS, false>(wave, tid < 21 * GS, [&] {          // thread (stream slot gi, unit uu): the unit's four gates
     const int gi = GS > 1 ? tid / 21 : 0, uu = GS > 1 ? tid % 21 : tid;
     f32x4 zz[4];      // (each chain starts from its first partial row -- a sum of FMAs from +0, never -0: adding it to zero changes nothing)
 #pragma unroll
@@ -1423,17 +1551,17 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
     st_next1(cx.sbc, static_cast<unsigned>((d.c_off + uu) * 4) + so, c_new);      // (h, c: the next frame's)
     st_next1(cx.sbc, static_cast<unsigned>((d.h_off + uu) * 4) + so, h_new);
     lds1(HN + gi * SGB + uu * 4) = h_new;
-  }
+  });
   FZ_WSTAMP(I, 5);
   lds_barrier();
   FZ_WSTAMP(I, 6);
   // Dense: output n of stream gi by thread (gi * dout + n) mod 512 (its row of the Dense kernel arrived in the carry: 512 is a multiple
   // of dout, so a thread's row is the same in every pass)
   constexpr int DPASS = (d.dout * GS + THREADS - 1) / THREADS;
-#pragma unroll
-  for (int ps = 0; ps < DPASS; ++ps) {
+  sfor<DPASS>([&](auto pp) {
+    constexpr int ps = decltype(pp)::value;
     const int idx = tid + THREADS * ps;
-    if (idx < d.dout * GS) {
+    role_block<0, d.dout * GS - THREADS * ps, false>(wave, idx < d.dout * GS, [&] {
       const int gi = GS > 1 ? idx >> clog2(d.dout) : 0, n = GS > 1 ? idx & (d.dout - 1) : tid;
       // (the roundings spelled out -- one product rounded, the other fused into the sum of the two -- as the compiler has always contracted
       //  `w0 h0 + w1 h1`: left to it, which of the pairs it fuses depends on how it happens to vectorise the two chains, and the rows change in
@@ -1450,8 +1578,8 @@ __device__ __forceinline__ void lstm_op(const Ctx& cx, int tid, Carry<I>& c, Car
       const int f = n >> XS, cc = n & (d.x_cols - 1);
       img_st1<d.x_fmt>(d.y_b + gi * d.x_gstride_b + f * d.x_pitch_b + cc * esz_of(d.x_fmt), d.x_plane_b, a);
       if constexpr (d.ldst_on) st_state1<d.nt0 != 0>(cx.sbc, static_cast<unsigned>((d.ldst_off + f * d.ldst_ld + cc) * 4) + gofs(cx, d.g0 + gi), a);
-    }
-  }
+    });
+  });
 }
 
 #if FZ_BASE
@@ -1568,7 +1696,7 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
         constexpr int i = decltype(ii)::value;
         const int f = rg + 32 * i;
         // (the first row replaces the zero; a column of -0 then leaves -0 where `0 + row` left +0, and the sum `m` below, which starts at +0, absorbs it)
-        if (f < d.F) { if constexpr (i == 0) s4 = fwd_ld4g<I>(gi, f, 4 * c4); else s4 += fwd_ld4g<I>(gi, f, 4 * c4); }
+        role_block<0, (d.F - 32 * i) * 16, false>(wave, f < d.F, [&] { if constexpr (i == 0) s4 = fwd_ld4g<I>(gi, f, 4 * c4); else s4 += fwd_ld4g<I>(gi, f, 4 * c4); });
       });
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -1602,10 +1730,10 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
 #pragma unroll
   for (int gi = 0; gi < GS; ++gi) {
     const f32x4 g4 = lds4(GATE + gi * SGB + 16 * c4);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
+    sfor<NI>([&](auto ii) {
+      constexpr int i = decltype(ii)::value;
       const int f = rg + 32 * i;
-      if (f < d.F) {
+      role_block<0, (d.F - 32 * i) * 16, false>(wave, f < d.F, [&] {
         const f32x4 x = fwd_ld4g<I>(gi, f, 4 * c4);      // (re-read: cheaper than 32 registers held across the gates)
         const f32x4 y = x * g4 + c.w[gi * NI + i];
         FZ_TRACE4(cx, d.g0 + gi, 1 + d.bidx, f, 64, 4 * c4, y);
@@ -1617,8 +1745,8 @@ __device__ __forceinline__ void ctfa_op(const Ctx& cx, int tid, Carry<I>& c, Car
           // (packed plans: a consumer that is not the next op of this stream reads the rows from HBM)
           if constexpr (d.d0_on) st_state<d.nt0 != 0>(d.d0_src == S_CUR ? cx.sbc : cx.sbs, static_cast<unsigned>((d.d0_off + f * d.d0_ld + 4 * c4) * 4) + gofs(cx, d.g0 + gi), y);
         }
-      }
-    }
+      });
+    });
   }
 }
 
@@ -1628,6 +1756,9 @@ __device__ __forceinline__ void run_op(const Ctx& cx, Carry<I>& c, Carry<I + 1>&
   constexpr OpD d = kOps[I];
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));          // per-op thread id: nothing derived from it is hoisted across ops
+  // (Tried: `__builtin_assume(0 <= tid < 512)` behind the pin.  Shifts become logical and 61 of the 272 v_mul_lo_u32 24-bit multiplies, but with the
+  //  offsets known not to wrap the compiler forms 64-bit vector addresses again -- v_lshl_add_u64 / v_add_co / v_addc 76 -> 518, 552 new v_bfe_i32,
+  //  365 instructions and 129 s_nop MORE than without it.  Left out)
   // (Tried in round 4: the index rebuilt per op from a scalar wave index + a volatile lane count, so that threadIdx.x is not live across
   //  all ops -- the 4-stream build spills it and re-loads it in every op prologue.  200 scratch loads fewer there, no change in its step
   //  time; the one-stream kernel 1 % slower (0.3777 -> 0.3813 ms, four alternating runs on one box).  Dropped.)
@@ -1666,7 +1797,7 @@ __device__ __forceinline__ void run_op(const Ctx& cx, Carry<I>& c, Carry<I + 1>&
 
   if constexpr (d.type == T_INPUT) {
     input_op<I>(cx, tid);
-    build_next<I>(tid, p1, c.p);
+    finish_op<I, WAVES>(tid, wave_of(tid), p1, c.p, [] {});
   } else if constexpr (d.type == T_CONV) {
     if constexpr (d.path == P_X16B) conv_x16b<I>(cx, tid, c, p1, p3);
     else conv_r32b<I>(cx, tid, c, p1, p3, wx);
@@ -1682,7 +1813,7 @@ __device__ __forceinline__ void run_op(const Ctx& cx, Carry<I>& c, Carry<I + 1>&
       // packed plans: an instance of the network's last CTFA that is followed by another stream's ops completes the image of the conv
       // after it (its loads went out in the prologue above) -- once every thread is done with the plain rows the image overlaps
       lds_barrier();
-      build_next<I>(tid, p1, c.p);
+      finish_op<I, WAVES>(tid, wave_of(tid), p1, c.p, [] {});
     }
   }
   if constexpr (d.drain && !DRAIN_FIRST) drain_vm();
