@@ -299,8 +299,41 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * both truncated to the input's length times the ratio.  A rate above 16 kHz is reduced on the way in and increased on the way out, 8 kHz
  * the other way round.  Each direction delays by K samples of the lower rate: nutls_pcm_delay_samples = 2 K max(1, rate / 16000) samples at
  * the caller's rate for the two together (0 at 16000); the one-hop lag of nutls_enhance_hop stays on top of it.
- * Band limit: a 32 or 48 kHz caller gets back audio band-limited to 8 kHz -- that is what the model produces.  Passing the upper band around
- * the model is out of scope.
+ *
+ * Upper band (32 and 48 kHz): the model runs at 16 kHz, so what it returns is band-limited to 8 kHz.  nutls_set_pcm_upper_band(h, gain), gain
+ * in 0 .. 1, passes the band above 8 kHz AROUND the model: it waits beside it for exactly the model's latency and is added back at that gain.
+ * With D the decode half, E the encode half, M the model path with its one-hop lag, q = rate / 16000 and S = 256 q, per stream
+ *   u[n]   = x[n - 2 K q] - E(D(x))[n]        the input, delayed by nutls_pcm_delay_samples, minus its own low band
+ *   out[n] = E(M(D(x)))[n] + gain * u[n - S]  (samples before a stream's first are zeros)
+ * The delay and the alignment are those without it: one hop plus nutls_pcm_delay_samples.  With M the identity and gain 1 the output is the
+ * delayed input, whatever the filter.  The crossover is the prototype's own, 1 - H^2: at most -76 dB up to 0.85 of 8 kHz (the noisy input's low
+ * band does not leak back), -15 dB at 0.95, -2.5 dB at 8 kHz, 0 dB from 1.05.
+ *   - gain 0, the default, is off: the _pcm entries are then exactly what they are without this call -- same kernels, same bits.
+ *   - A gain that is NaN or outside 0 .. 1 is NUTLS_ERR_ARG and changes nothing.  So is a gain other than 0 on a handle whose rate is 8000 or
+ *     16000: there is no band above 8 kHz there, and an explicit request never silently does nothing.
+ *   - The call is allowed between any two hops.  Like a format switch it synchronises the device and zeroes every stream's resampler
+ *     histories and upper-band state.  Setting the value the handle already has is a no-op that touches nothing.  nutls_pcm_upper_band reads
+ *     the gain back.  nutls_set_pcm_format turns the upper band OFF (gain 0), because a new format starts anew: set the gain after the format.
+ *   - Every _pcm entry honours the gain, in the two launches it already makes: hop, _active, _host, _host_active, block, block _host and the
+ *     _ragged entries; hop fusion on or off makes no difference.  So do the halves: nutls_pcm_decode_hop / _block(_ragged) record u of what they
+ *     decode, nutls_pcm_encode_hop / _block(_ragged) add gain * u that belongs to the handle's LAST DECODED hop or block -- the contract
+ *     nutls_istft_block has with the last analysed block: same n_hops, same counts, same mask.  Their signatures are what they were.
+ *   - State, per stream (utterance), outside the signature's tensors, allocated when a gain other than 0 is first set: the last 2 K decoded
+ *     samples and the last hop of u.  It obeys the rules of the resampler history below (nutls_reset, held streams, blocks, ragged counts --
+ *     a count k carries it from hop k - 1, k = 0 holds it --, refusals before the first conversion).
+ *   - Operation order, fp32, the same sequence for every output sample wherever it lies in its hop or block and whichever entry runs it:
+ *       d[m]   = the rate reduction's sum: taps ascending, one FMA each, from 0                                 (2 K q + 1 FMAs)
+ *       c[n]   = the rate increase's sum over d: taps ascending, one FMA each, from 0, the zero-stuffed terms skipped, WITHOUT its product
+ *                by q                                                                                           (at most 2 K + 1 FMAs)
+ *       u[n]   = fma(-q, c[n], x[n - 2 K q])                                                                    (one FMA)
+ *       z[n]   = the output sample without the upper band (the rate increase's sum over the model's output, then its product by q)
+ *       out[n] = fma(gain, u[n - S], z[n])                                                                      (one FMA)
+ *     The longest path of an output sample has N = 2 K q + 2 K + 4 roundings; its error is at most (N + 3) 2^-24 times
+ *     q sum |p| |M(D(x))| + gain (|x[n - 2 K q - S]| + q sum |p| (sum |p| |x|)), the absolute products along those sums.
+ *     int16 output is that float, rounded to nearest even and saturated: bit for bit what NUTLS_PCM_F32 returns, then quantised.
+ *   - In place: the _pcm device entries read pcm_in in their decode launch only, which has run before the encode launch writes pcm_out, so
+ *     pcm_in == pcm_out (the same base pointer; no other overlap) is allowed, with the upper band on as with it off: u waits in a library buffer.
+ *   - Cost: README, "PCM gateway".  Out of scope: a gain that follows the model's suppression (the "follow" mode of band-split suppressors).
  *
  * State: per stream (utterance) and direction the library keeps the filter's last 2 K q input samples, outside the signature's tensors.
  * nutls_reset(h, b) zeroes stream b's (-1: everybody's).  A held stream (active[b] == 0) keeps it as it is -- neither kernel touches it -- and
@@ -319,7 +352,12 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * _pcm_ragged entries at the end of this section.  Zero-copy reads of pinned PCM stay out of scope: the _host entries copy. */
 #define NUTLS_PCM_F32 0   /* float32, unit scale (what nutls_enhance_hop takes) */
 #define NUTLS_PCM_S16 1   /* int16, little endian; 32768 = 1.0 */
-int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);
+int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);   /* also turns the upper band off (gain 0) */
+/* "Upper band" above.  gain in 0 .. 1, 0 = off (the default); NaN, a gain outside 0 .. 1, or a gain other than 0 at 8000 / 16000 Hz:
+ * NUTLS_ERR_ARG, nothing changes.  Synchronises and zeroes every stream's resampler histories and upper-band state, unless the gain is the
+ * one the handle already has.  nutls_set_pcm_format resets it to 0: call this after it. */
+int nutls_set_pcm_upper_band(nutls_handle* h, float gain);
+int nutls_pcm_upper_band(nutls_handle* h, float* gain);      /* the gain in force */
 int nutls_pcm_hop_samples(nutls_handle* h);     /* S = 256 * rate / 16000: 128, 256, 512, 768 */
 int nutls_pcm_delay_samples(nutls_handle* h);   /* delay of the two rate conversions together, in samples at the caller's rate */
 int nutls_pcm_filter_taps(int rate_hz);         /* host only, no handle: 2 K q + 1; 1 for 16000; -1 for an unsupported rate */

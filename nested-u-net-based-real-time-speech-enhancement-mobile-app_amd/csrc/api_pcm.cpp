@@ -4,6 +4,8 @@
 // nutls_enhance_hop_active, nutls_enhance_block) on library buffers and encodes: the model path, the masks, hop fusion and the state
 // coherence are that code, not copies of it.  At 16000 / float32 the entries ARE the plain ones (forwarded before anything else happens).
 // The _pcm_ragged block entries do the same around nutls_enhance_block_ragged, with the per-utterance hop counts handed to both kernels.
+// Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): with a gain other than 0 decode_launch / encode_launch start the kernels that also
+// form and add the band above 8 kHz -- every entry below goes through those two, so every entry honours the gain; with 0 nothing here differs.
 // The kernels: pcm.hip.
 #include <cstdint>
 
@@ -42,22 +44,52 @@ int pcm_init(Engine* e) {
   return NUTLS_OK;
 }
 
+// The upper band's buffers (nutls_set_pcm_upper_band), allocated when a gain other than 0 is first set -- after pcm_init.
+int upper_init(Engine* e) {
+  PcmState& st = e->pcm;
+  if (st.upper_ready) return NUTLS_OK;
+  const size_t rows = static_cast<size_t>(st.rows);
+  int rc;
+  if ((rc = dev_alloc_once(e, rows * kPcmUpCtx, &st.up_ctx[0], true)) || (rc = dev_alloc_once(e, rows * kPcmUpCtx, &st.up_ctx[1], true)) ||
+      (rc = dev_alloc_once(e, rows * kPcmMaxHop, &st.up_last[0], true)) || (rc = dev_alloc_once(e, rows * kPcmMaxHop, &st.up_last[1], true)) ||
+      (rc = dev_alloc_once(e, rows * max_hops(e) * kPcmMaxHop, &st.up_u, true)))
+    return rc;
+  st.upper_ready = true;
+  return NUTLS_OK;
+}
+
+// Row idx's (< 0: every row's) resampler histories and upper-band state, where they exist.  (up_u is not state: the encode half reads only what
+// the decode half of the same hop or block wrote there.)
 int zero_histories(Engine* e, int idx) {
   PcmState& st = e->pcm;
   if (!st.ready) return NUTLS_OK;
-  for (float* p : {st.hist_dec[0], st.hist_dec[1], st.hist_enc[0], st.hist_enc[1]}) {
-    if (idx < 0) HIP_TRY(hipMemset(p, 0, static_cast<size_t>(st.rows) * kPcmMaxHist * sizeof(float)));
-    else HIP_TRY(hipMemset(p + static_cast<size_t>(idx) * kPcmMaxHist, 0, kPcmMaxHist * sizeof(float)));
+  auto zero = [&](float* p, size_t stride) -> int {
+    if (idx < 0) HIP_TRY(hipMemset(p, 0, static_cast<size_t>(st.rows) * stride * sizeof(float)));
+    else HIP_TRY(hipMemset(p + static_cast<size_t>(idx) * stride, 0, stride * sizeof(float)));
+    return NUTLS_OK;
+  };
+  for (float* p : {st.hist_dec[0], st.hist_dec[1], st.hist_enc[0], st.hist_enc[1]})
+    if (int rc = zero(p, kPcmMaxHist)) return rc;
+  if (!st.upper_ready) return NUTLS_OK;
+  for (int i = 0; i < 2; ++i) {
+    if (int rc = zero(st.up_ctx[i], kPcmUpCtx)) return rc;
+    if (int rc = zero(st.up_last[i], kPcmMaxHop)) return rc;
   }
   return NUTLS_OK;
 }
 
 // One launch of a half.  A block call (offline handle) flips the history buffers; a hop call (streaming handle) works in place on buffer 0.
 // counts: the DEVICE counts of a ragged block or null (the flip is the whole handle's: the kernel carries a held row's history across).
+// With the upper band on (a gain other than 0) the launch is the kernel that also forms / adds it; its carried state flips with the histories.
 int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
-  HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  if (st.upper != 0.f) {
+    const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
+    HIP_TRY(launch_pcm_decode_upper(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
+  } else {
+    HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  }
   st.dec_par = nxt;
   return NUTLS_OK;
 }
@@ -65,7 +97,12 @@ int decode_launch(Engine* e, const void* in, float* out, const unsigned char* ac
 int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
-  HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  if (st.upper != 0.f) {
+    const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
+    HIP_TRY(launch_pcm_encode_upper(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
+  } else {
+    HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+  }
   st.enc_par = nxt;
   return NUTLS_OK;
 }
@@ -205,12 +242,14 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
   if (!e->pcm.ready && to_plain) {      // nothing has been converted yet and nothing will be
     e->pcm.rate = rate_hz;
     e->pcm.fmt = sample_format;
+    e->pcm.upper = 0.f;
     return NUTLS_OK;
   }
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());      // queued conversions still read the taps and histories that change below
   e->pcm.rate = rate_hz;
   e->pcm.fmt = sample_format;
+  e->pcm.upper = 0.f;                   // a new format starts anew: the upper band is off until nutls_set_pcm_upper_band
   if (!e->pcm.ready) {
     if (int rc = pcm_init(e)) return rc;      // (uploads the taps, zeroes the histories)
   } else {
@@ -218,6 +257,31 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
     if (int rc = zero_histories(e, -1)) return rc;      // a format switch starts a new history for every stream
   }
   HIP_TRY(hipDeviceSynchronize());
+  return NUTLS_OK;
+}
+
+int nutls_set_pcm_upper_band(nutls_handle* h, float gain) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_upper_band: null handle");
+  if (!(gain >= 0.f && gain <= 1.f)) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_upper_band: gain must lie in 0 .. 1");      // (NaN fails both)
+  Engine* e = &h->eng;
+  if (gain == e->pcm.upper) return NUTLS_OK;      // nothing is touched
+  if (gain != 0.f && e->pcm.rate <= 16000)
+    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_upper_band: the handle's rate is " + std::to_string(e->pcm.rate) +
+                                   " Hz: there is no band above 8 kHz (nutls_set_pcm_format with 32000 or 48000 first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // queued conversions still read the histories and the upper-band state that change below
+  if (int rc = pcm_init(e)) return rc;
+  if (gain != 0.f)
+    if (int rc = upper_init(e)) return rc;
+  if (int rc = zero_histories(e, -1)) return rc;      // like a format switch: every stream starts anew, resamplers and upper band
+  e->pcm.upper = gain == 0.f ? 0.f : gain;
+  HIP_TRY(hipDeviceSynchronize());
+  return NUTLS_OK;
+}
+
+int nutls_pcm_upper_band(nutls_handle* h, float* gain) {
+  if (!h || !gain) return fail(NUTLS_ERR_ARG, "nutls_pcm_upper_band: null pointer");
+  *gain = h->eng.pcm.upper;
   return NUTLS_OK;
 }
 

@@ -242,7 +242,7 @@ int build_offline_plan(Engine* e);
 int upload_counts(Engine* e, const int* counts, int n, const char* who);
 
 // ---- api_pcm.cpp -----------------------------------------------------------------------------
-// nutls_reset: zero the resampler histories of row `idx` (stream / utterance; < 0: every row's) where they exist
+// nutls_reset: zero the resampler histories and the upper-band state of row `idx` (stream / utterance; < 0: every row's) where they exist
 int pcm_reset(Engine* e, int idx);
 
 }  // namespace nutls

@@ -15,6 +15,16 @@
 // of hop k - 1 writes the history, a hop behind k returns before 1. with a zero hop; k == 0 holds the row, and because a block call flips the
 // history buffers of the whole handle, the workgroup of its hop 0 copies the row's history across.
 // Cost: 256 * 145 FMAs per stream and hop at most (48 kHz decode); the launch, not the arithmetic, is what a hop pays for.
+// Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): the band above 8 kHz goes around the model inside the same two launches, in two more
+// kernels of the same body (pcm_hop<..., UPPER>, see there) -- the kernels above are the ones a gain of 0 runs.  Per caller sample n of a stream,
+// each a fixed sequence of fp32 operations wherever the hop or block boundary falls:
+//   d[m]   = the decode chain: taps ascending, one FMA each, from 0                                      (2 K q + 1 FMAs)
+//   c[n]   = the encode chain over d: taps r, r + q, ... ascending, one FMA each, from 0, WITHOUT its product by q   (2 K + 1 FMAs at r = 0, else 2 K)
+//   u[n]   = fmaf(-q, c[n], x[n - 2 K q])                                                                  (one FMA)
+//   z[n]   = the encode chain over the model's output, times q: the sample a gain of 0 returns
+//   out[n] = fmaf(gain, u[n - S], z[n])                                                                    (one FMA)
+// The longest path of an output sample has 2 K q + 2 K + 4 roundings (d, c, u, out).  +49 FMAs per caller sample in the decode, and the 2 K
+// decoded samples of context computed again by every hop of a block but its first (+19 % of the decode chains); the encode adds one FMA.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,23 +50,31 @@ struct Rate {
 // x: the staged samples in LDS, x[0] = the oldest sample of the left context (hist samples), x[hist] = the hop's first.
 // DOWN (rate reduction by Q):  y[n] = sum_j p[j] x[Q n - j],                j = 0 .. 2 K Q
 // UP   (rate increase by Q):   z[n] = Q sum_i p[r + Q i] x[m - i],  n = Q m + r,  i = 0 .. 2 K (r = 0) or 2 K - 1   (zero-stuffing, then Q p)
+// pcm_up_chain: the chain of UP without its last step, the product by Q (the upper band folds that product into its subtraction).
+template <int Q>
+__device__ __forceinline__ float pcm_up_chain(const float* p, const float* x, int n) {
+  constexpr int K = Rate<Q>::k;
+  float acc = 0.f;
+  const int m = n / Q, r = n - m * Q;
+  const float* at = x + 2 * K + m;
+  const float* pr = p + r;
+#pragma unroll 8
+  for (int i = 0; i < 2 * K; ++i) acc = fmaf(pr[Q * i], at[-i], acc);
+  if (r == 0) acc = fmaf(p[2 * K * Q], at[-2 * K], acc);
+  return acc;
+}
+
 template <int Q, bool UP>
 __device__ __forceinline__ float pcm_fir(const float* p, const float* x, int n) {
   constexpr int K = Rate<Q>::k;
-  float acc = 0.f;
   if constexpr (!UP) {
+    float acc = 0.f;
     const float* at = x + 2 * K * Q + Q * n;
 #pragma unroll 8
     for (int j = 0; j <= 2 * K * Q; ++j) acc = fmaf(p[j], at[-j], acc);
     return acc;
   } else {
-    const int m = n / Q, r = n - m * Q;
-    const float* at = x + 2 * K + m;
-    const float* pr = p + r;
-#pragma unroll 8
-    for (int i = 0; i < 2 * K; ++i) acc = fmaf(pr[Q * i], at[-i], acc);
-    if (r == 0) acc = fmaf(p[2 * K * Q], at[-2 * K], acc);
-    return acc * static_cast<float>(Q);
+    return pcm_up_chain<Q>(p, x, n) * static_cast<float>(Q);
   }
 }
 
@@ -107,17 +125,30 @@ __device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
 }
 
 // ---- one hop of one row: NIN samples in, NIN / Q (DOWN) or NIN * Q (UP) out --------------------------------------------------------------------
-template <int Q, bool UP, int NIN, typename TI, typename TO>
+// UPPER (nutls_set_pcm_upper_band; rates above 16 kHz, so DOWN is the decode half and UP the encode half; ub: pcm.hpp, PcmUpper):
+//   decode: after the hop's decoded samples d, u[n] = fmaf(-Q, c[n], x[n - 2 K Q]) for the hop's S = NIN caller samples, c[n] = pcm_up_chain over
+//           d with its 2 K samples of left context (the UP chain without its product: E(D(x))[n] = Q c[n]), written to ub.u.  That context is the
+//           carried one (ub.carry_in) for a row's first hop; a later hop of a block COMPUTES it -- the same chains over the same samples, so the
+//           same bits -- from 2 K Q more input samples of the row (the decoded hop in front of it is another workgroup's of the same launch);
+//   encode: out[n] = fmaf(gain, u'[n], z[n]), z the sample without the upper band, u' the u of the hop in front: ub.u's for a later hop of a
+//           block, the carried one (ub.carry_in) for the first.  The workgroup of the row's last real hop carries that hop's u on.
+template <int Q, bool UP, int NIN, typename TI, typename TO, bool UPPER = false>
 __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                        const int* counts, int n_hops) {
+                                        const int* counts, int n_hops, const PcmUpper ub = PcmUpper{}) {
   constexpr int K = Rate<Q>::k;
   constexpr int HIST = UP ? 2 * K : 2 * K * Q;      // samples of left context
   constexpr int NOUT = UP ? NIN * Q : NIN / Q;
+  constexpr bool DEC_UPPER = UPPER && !UP, ENC_UPPER = UPPER && UP;
+  constexpr int XPRE = DEC_UPPER ? HIST : 0;        // input samples in front of the left context: what the decoded context is computed from
+  constexpr int YPRE = DEC_UPPER ? 2 * K : 0;       // decoded samples of left context in front of the hop's
+  constexpr int CARRY = DEC_UPPER ? kPcmUpCtx : kPcmMaxHop, NCARRY = DEC_UPPER ? YPRE : NOUT;      // a row's carried upper-band state: stride, floats in use
   static_assert(HIST <= kPcmMaxHist && HIST <= NIN && NIN <= kPcmMaxHop && NOUT <= kPcmMaxHop, "staging sizes");
   static_assert(HIST % 8 == 0 && NIN % 8 == 0 && NOUT % 8 == 0, "16-byte accesses");
-  __shared__ __attribute__((aligned(16))) float s_x[kPcmMaxHist + kPcmMaxHop];
+  static_assert(!UPPER || (Q > 1 && YPRE == (DEC_UPPER ? kPcmUpCtx : 0) && YPRE + NOUT <= kPcmMaxHop && XPRE + HIST <= NIN && XPRE % 8 == 0 && YPRE % 8 == 0), "upper band: staging sizes");
+  __shared__ __attribute__((aligned(16))) float s_x[(DEC_UPPER ? kPcmMaxHist : 0) + kPcmMaxHist + kPcmMaxHop];
   __shared__ __attribute__((aligned(16))) float s_y[kPcmMaxHop];
   __shared__ float s_p[Rate<kPcmMaxQ>::taps];
+  float* const xs = s_x + XPRE;      // xs[0] = the oldest sample of the left context
   const int t = blockIdx.x, row = blockIdx.y, tid = threadIdx.x;
   TO* const dst = out + (static_cast<size_t>(row) * n_hops + t) * NOUT;
   if (active && !active[row]) {      // (the whole workgroup: the flag is per row)
@@ -132,6 +163,11 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
         const f32x4* const from = reinterpret_cast<const f32x4*>(hist_in + static_cast<size_t>(row) * kPcmMaxHist);
         f32x4* const to = reinterpret_cast<f32x4*>(hist_out + static_cast<size_t>(row) * kPcmMaxHist);
         for (int i = tid; i < HIST / 4; i += kThreads) to[i] = from[i];
+        if constexpr (UPPER) {       // and so does its upper-band state
+          const f32x4* const ufrom = reinterpret_cast<const f32x4*>(ub.carry_in + static_cast<size_t>(row) * CARRY);
+          f32x4* const uto = reinterpret_cast<f32x4*>(ub.carry_out + static_cast<size_t>(row) * CARRY);
+          for (int i = tid; i < NCARRY / 4; i += kThreads) uto[i] = ufrom[i];
+        }
       }
     }
     return;
@@ -139,18 +175,42 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
   const TI* const src = in + (static_cast<size_t>(row) * n_hops + t) * NIN;
   for (int i = tid; i < Rate<Q>::taps; i += kThreads) s_p[i] = taps[i];
   if constexpr (HIST > 0) {
-    if (t > 0) stage_in(src - HIST, s_x, HIST, tid);
-    else stage_in(hist_in + static_cast<size_t>(row) * kPcmMaxHist, s_x, HIST, tid);
+    if (t > 0) {
+      stage_in(src - HIST - XPRE, s_x, HIST + XPRE, tid);
+    } else {
+      stage_in(hist_in + static_cast<size_t>(row) * kPcmMaxHist, xs, HIST, tid);
+      if constexpr (DEC_UPPER) stage_in(ub.carry_in + static_cast<size_t>(row) * CARRY, s_y, YPRE, tid);
+    }
   }
-  stage_in(src, s_x + HIST, NIN, tid);
+  stage_in(src, xs + HIST, NIN, tid);
   __syncthreads();
   if constexpr (HIST > 0) {
     // the history the next call starts from: the row's last real hop's.  hist_out may be hist_in only where this workgroup is also the one that read it (n_hops == 1)
-    if (t == k - 1) stage_out(s_x + NIN, hist_out + static_cast<size_t>(row) * kPcmMaxHist, HIST, tid);
+    if (t == k - 1) stage_out(xs + NIN, hist_out + static_cast<size_t>(row) * kPcmMaxHist, HIST, tid);
   }
-  for (int n = tid; n < NOUT; n += kThreads) s_y[n] = pcm_fir<Q, UP>(s_p, s_x, n);
+  if constexpr (DEC_UPPER) {
+    // s_y = [2 K decoded samples of context | the hop's 256]: a later hop of a block computes the context, the first one has staged it
+    for (int n = tid + (t > 0 ? 0 : YPRE); n < YPRE + NOUT; n += kThreads) s_y[n] = pcm_fir<Q, false>(s_p, xs, n - YPRE);
+    __syncthreads();
+    stage_out(s_y + YPRE, dst, NOUT, tid);
+    if (t == k - 1) stage_out(s_y + NOUT, ub.carry_out + static_cast<size_t>(row) * CARRY, YPRE, tid);      // (read before the first barrier, by this workgroup, where it is carry_in)
+    // u over the staged input, in place: xs[n] = x[n - 2 K Q] of the hop's sample n, and sample n is thread n's alone (the chain reads s_y and s_p)
+    for (int n = tid; n < NIN; n += kThreads) xs[n] = fmaf(-static_cast<float>(Q), pcm_up_chain<Q>(s_p, s_y, n), xs[n]);
+    __syncthreads();
+    stage_out(xs, ub.u + (static_cast<size_t>(row) * n_hops + t) * NIN, NIN, tid);
+    return;
+  }
+  if constexpr (ENC_UPPER) {
+    const float* const before = t > 0 ? ub.u + (static_cast<size_t>(row) * n_hops + t - 1) * NOUT : ub.carry_in + static_cast<size_t>(row) * CARRY;
+    for (int n = tid; n < NOUT; n += kThreads) s_y[n] = fmaf(ub.gain, before[n], pcm_fir<Q, UP>(s_p, xs, n));
+  } else {
+    for (int n = tid; n < NOUT; n += kThreads) s_y[n] = pcm_fir<Q, UP>(s_p, xs, n);
+  }
   __syncthreads();
   stage_out(s_y, dst, NOUT, tid);
+  if constexpr (ENC_UPPER) {      // behind the barrier: where carry_out is carry_in (n_hops == 1), every lane has read it.  (stage_out from global memory: a 16-byte copy)
+    if (t == k - 1) stage_out(ub.u + (static_cast<size_t>(row) * n_hops + t) * NOUT, ub.carry_out + static_cast<size_t>(row) * CARRY, NOUT, tid);
+  }
 }
 
 // caller samples -> 16 kHz float32: a rate above 16 kHz is reduced, 8 kHz is doubled
@@ -165,6 +225,19 @@ template <int Q, bool UP, typename TO>
 __global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
                                                               const unsigned char* active, const int* counts, int n_hops) {
   pcm_hop<Q, UP, 256, float, TO>(in, out, taps, hist_in, hist_out, active, counts, n_hops);
+}
+
+// The two with the upper band: rates above 16 kHz only (decode reduces, encode increases)
+template <int Q, typename TI>
+__global__ __launch_bounds__(kThreads) void pcm_decode_upper_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
+                                                                    const unsigned char* active, const int* counts, int n_hops, PcmUpper ub) {
+  pcm_hop<Q, false, 256 * Q, TI, float, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub);
+}
+
+template <int Q, typename TO>
+__global__ __launch_bounds__(kThreads) void pcm_encode_upper_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
+                                                                    const unsigned char* active, const int* counts, int n_hops, PcmUpper ub) {
+  pcm_hop<Q, true, 256, float, TO, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub);
 }
 
 template <int Q, bool UP, typename T>
@@ -252,6 +325,42 @@ hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, cons
     default: return hipErrorInvalidValue;
   }
 #undef NUTLS_PCM_ENCODE
+}
+
+hipError_t launch_pcm_decode_upper(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s) {
+  const dim3 grid(n_hops, rows), block(kThreads);
+#define NUTLS_PCM_DECODE_UPPER(Q, T) \
+  hipLaunchKernelGGL((pcm_decode_upper_kernel<Q, T>), grid, block, 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out, active, counts, n_hops, ub)
+  if (rate_hz == 32000) {
+    if (s16) NUTLS_PCM_DECODE_UPPER(2, short);
+    else NUTLS_PCM_DECODE_UPPER(2, float);
+  } else if (rate_hz == 48000) {
+    if (s16) NUTLS_PCM_DECODE_UPPER(3, short);
+    else NUTLS_PCM_DECODE_UPPER(3, float);
+  } else {
+    return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_DECODE_UPPER
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm_encode_upper(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s) {
+  const dim3 grid(n_hops, rows), block(kThreads);
+#define NUTLS_PCM_ENCODE_UPPER(Q, T) \
+  hipLaunchKernelGGL((pcm_encode_upper_kernel<Q, T>), grid, block, 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out, active, counts, n_hops, ub)
+  if (rate_hz == 32000) {
+    if (s16) NUTLS_PCM_ENCODE_UPPER(2, short);
+    else NUTLS_PCM_ENCODE_UPPER(2, float);
+  } else if (rate_hz == 48000) {
+    if (s16) NUTLS_PCM_ENCODE_UPPER(3, short);
+    else NUTLS_PCM_ENCODE_UPPER(3, float);
+  } else {
+    return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_ENCODE_UPPER
+  return hipGetLastError();
 }
 
 }  // namespace nutls

@@ -16,6 +16,7 @@ constexpr int kPcmK = 24;                        // low-rate samples of delay pe
 constexpr int kPcmMaxQ = 3;
 constexpr int kPcmMaxHist = 2 * kPcmK * kPcmMaxQ;      // floats of history per row and direction (the longest: 48 kHz decode)
 constexpr int kPcmMaxHop = 256 * kPcmMaxQ;             // samples of a hop at the highest rate
+constexpr int kPcmUpCtx = 2 * kPcmK;                   // upper band: decoded samples of left context the decode half carries per row
 
 // q of a supported rate (8000, 16000, 32000, 48000), else 0
 int pcm_ratio(int rate_hz);
@@ -38,6 +39,23 @@ struct PcmState {
   float *f_in = nullptr, *f_out = nullptr;       // 16 kHz float32 around the model: [B, 256] / [utterances, max_frames * 256]
   unsigned char *raw_in = nullptr, *raw_out = nullptr;      // the _host entries' staging of the callers' samples (allocated on first use, sized for float32 at 48 kHz)
   unsigned char* d_active = nullptr;             // [B] device copy of the mask of nutls_enhance_hop_pcm_host_active
+  // Upper band (nutls_set_pcm_upper_band; 32 / 48 kHz only): u = the delayed input minus its own low band, formed by the decode half and added
+  // one hop later, times the gain, by the encode half.  Allocated when a gain other than 0 is first set; zeroed with the histories above.
+  float upper = 0.f;                   // the gain; 0: off -- the launches are the ones without the upper band
+  bool upper_ready = false;            // the buffers below exist
+  float* up_ctx[2] = {nullptr, nullptr};       // [rows][kPcmUpCtx] the last 2 K DECODED samples (the left context of E(D(x))); flips with dec_par
+  float* up_last[2] = {nullptr, nullptr};      // [rows][kPcmMaxHop] u of the last real hop the encode half has seen the decode of; flips with enc_par
+  float* up_u = nullptr;               // [rows, n_hops * S] u of the last decoded hop / block (written by the decode half, read by the encode half)
+};
+
+// What a launch with the upper band gets on top (by value).  Decode: u = where the hops' u goes, [rows, n_hops * S]; carry_in / carry_out =
+// [rows][kPcmUpCtx] decoded context.  Encode: u = the same buffer, read; carry_in / carry_out = [rows][kPcmMaxHop], the u of the hop in front of
+// the call's first.  carry_in and carry_out follow the rules of hist_in and hist_out.  gain: the encode half's.
+struct PcmUpper {
+  float gain;
+  float* u;
+  const float* carry_in;
+  float* carry_out;
 };
 
 // Caller samples -> 16 kHz float32.  grid (n_hops, rows).  in: [rows, n_hops * S] of the format; out: [rows, n_hops * 256].  hist_in / hist_out:
@@ -50,5 +68,10 @@ hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, cons
 // 16 kHz float32 -> caller samples; the same conventions the other way round.
 hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
                              const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
+// The same two with the upper band (rate_hz 32000 or 48000, else hipErrorInvalidValue): other kernels, the ones above are not touched.
+hipError_t launch_pcm_decode_upper(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s);
+hipError_t launch_pcm_encode_upper(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s);
 
 }  // namespace nutls

@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "nutls_pcm_decode_hop", "nutls_pcm_encode_hop",
     "nutls_enhance_block_pcm", "nutls_enhance_block_pcm_host", "nutls_pcm_decode_block", "nutls_pcm_encode_block",
     "nutls_enhance_block_pcm_ragged", "nutls_enhance_block_pcm_ragged_host", "nutls_pcm_decode_block_ragged", "nutls_pcm_encode_block_ragged",
+    "nutls_set_pcm_upper_band", "nutls_pcm_upper_band",
 )
 
 
@@ -160,6 +161,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_enhance_block_pcm_ragged_host.argtypes = [vp, vp, vp, c.c_int, c.POINTER(c.c_int), c.c_int]
         lib.nutls_pcm_decode_block_ragged.argtypes = [vp, vp, vp, c.c_int, vp, vp]
         lib.nutls_pcm_encode_block_ragged.argtypes = [vp, vp, vp, c.c_int, vp, vp]
+    if not dev_lib or hasattr(lib, "nutls_set_pcm_upper_band"):
+        lib.nutls_set_pcm_upper_band.argtypes = [c.c_void_p, c.c_float]
+        lib.nutls_pcm_upper_band.argtypes = [c.c_void_p, fp]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -242,13 +246,28 @@ class _PcmFormat:
 
     def set_pcm_format(self, rate: int = 16000, dtype="float32") -> None:
         """What the ``_pcm`` methods take and return from now on: ``rate`` 8000, 16000, 32000 or 48000, ``dtype`` "float32" or "int16"
-        (32768 = 1.0).  May be called between any two hops; every stream's resampler history restarts from zeros.  The other methods keep
-        taking float32 at 16 kHz."""
+        (32768 = 1.0).  May be called between any two hops; every stream's resampler history restarts from zeros and the upper band
+        (``set_pcm_upper_band``) is off again.  The other methods keep taking float32 at 16 kHz."""
         name = np.dtype(dtype).name
         if name not in self._PCM_FORMATS:
             raise ValueError("dtype must be float32 or int16, got %s" % name)
         _check(self._lib, self._lib.nutls_set_pcm_format(self._h, int(rate), self._PCM_FORMATS[name]))
         self.pcm_rate, self.pcm_dtype = int(rate), name
+
+    def set_pcm_upper_band(self, gain: float) -> None:
+        """The band above 8 kHz of a 32 or 48 kHz caller, passed around the model and added back at ``gain`` in [0, 1], aligned with the
+        enhanced low band (``nutls_set_pcm_upper_band``); 0.0, the default, is off: the ``_pcm`` methods then return audio band-limited to
+        8 kHz, bit for bit as without this call.  May be called between any two hops: every stream's resampler history and upper-band state
+        restart from zeros (nothing happens when ``gain`` is the value in force).  ``set_pcm_format`` turns it off, so call this after it.
+        ``ValueError``: NaN, a gain outside [0, 1], or a gain other than 0 at 8000 / 16000 Hz."""
+        _check(self._lib, self._lib.nutls_set_pcm_upper_band(self._h, float(gain)))
+
+    @property
+    def pcm_upper_band(self) -> float:
+        """The upper band's gain in force (``nutls_pcm_upper_band``); 0.0: off."""
+        g = ctypes.c_float(0.0)
+        _check(self._lib, self._lib.nutls_pcm_upper_band(self._h, ctypes.byref(g)))
+        return float(g.value)
 
     @property
     def pcm_hop_samples(self) -> int:
@@ -1092,12 +1111,14 @@ class NutlsOffline(_PcmFormat):
             out[:, a * S:b * S] = block(np.ascontiguousarray(padded[:, a * S:b * S]))
         return out[:, lag:lag + n]
 
-    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge") -> np.ndarray:
+    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge", upper_gain: float = 0.0) -> np.ndarray:
         """A whole recording in its own format: ``wave [N]`` (one utterance) or ``[utterances, N]``, int16 or float32 numpy array of any
         length at ``rate`` (8000, 16000, 32000, 48000) -> the enhanced recording of the same shape and dtype, ALIGNED with the input:
         sample i of the result belongs to ``wave[i]`` (the input is padded with zeros to whole hops plus the total lag, one hop plus
         ``pcm_delay_samples``, and that lag is dropped from the front).  Sets the handle's format (``set_pcm_format``: the rate conversion
-        starts from a zero history); the model state carries on from earlier calls until :meth:`reset`."""
+        starts from a zero history); the model state carries on from earlier calls until :meth:`reset`.  ``upper_gain``: the gain of the band
+        above 8 kHz of a 32 or 48 kHz recording, passed around the model (``set_pcm_upper_band``, set after the format); 0.0: the result is
+        band-limited to 8 kHz."""
         self._dc(dc_mode)
         x = np.asarray(wave)
         if x.dtype.name not in self._PCM_FORMATS:
@@ -1108,6 +1129,7 @@ class NutlsOffline(_PcmFormat):
         if x.ndim != 2 or x.shape[0] != self.utterances:
             raise ValueError("wave must be [%sN], got %s" % ("%d," % self.utterances if self.utterances > 1 else "", np.shape(wave)))
         self.set_pcm_format(rate, x.dtype)
+        self.set_pcm_upper_band(upper_gain)
         lag = self.pcm_hop_samples + self.pcm_delay_samples
         out = self._wave_through_blocks(x, lag, lambda blk: self.enhance_block_pcm_host(blk, None, dc_mode))
         return out if batched else out[0]
@@ -1169,7 +1191,8 @@ class NutlsOffline(_PcmFormat):
         :meth:`enhance` of a fresh one-utterance handle returns for it.  Every slot that was used starts from a reset.
         ``rate`` (8000, 16000, 32000, 48000): the recordings are in the callers' format, int16 or float32 arrays at that rate, all of one
         dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
-        handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format."""
+        handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format, which turns the upper band
+        (``set_pcm_upper_band``) off: the results are band-limited to 8 kHz."""
         dc = self._dc(dc_mode)
         if rate is not None:
             return self._enhance_many_pcm(waves, dc, rate)
