@@ -123,7 +123,8 @@ int nutls_step_host_active(nutls_handle* h, const float* mag_in, float* mag_out,
 /* Page-locked, device-visible host memory for the buffers handed to nutls_step_host / nutls_enhance_hop_host / nutls_process_block_host
  * (what TF-Lite's interpreter.tensor(i) zero-copy view is to set_tensor / get_tensor in the reference's loop, interpreter_proposed.py:215-350:
  * the caller produces its frames in, and consumes its results from, memory the device can reach).  NULL on failure (nutls_last_error).
- * A handle is not needed; the memory is visible to every device. */
+ * A handle is not needed; the memory is visible to every device.  A buffer counts as page-locked when all of it lies inside ONE such
+ * allocation (any offset); one that starts inside an allocation and runs past its end takes the staged copies of pageable memory. */
 void* nutls_host_alloc(size_t bytes);
 void nutls_host_free(void* p);
 

@@ -1,8 +1,10 @@
 // Streaming entry points of the C ABI (include/nutls.h): the frame step and the hop (STFT analysis, step, inverse STFT; three launches or the
 // single launch of nutls_set_hop_fusion), each from device or host buffers and with or without a per-stream active mask, and the page-locked
 // host buffers the _host entries recognise.  The engine they drive: engine.cpp.
+#include <cstring>
 #include <map>
 #include <mutex>
+#include <vector>
 
 #include "engine.hpp"
 
@@ -42,6 +44,41 @@ static bool host_pinned(const void* p, size_t bytes) {
   --it;
   return static_cast<const char*>(p) + bytes <= it->first + it->second;
 }
+
+// A buffer that starts inside one of our page-locked allocations and runs past its end.  The runtime finds the allocation behind such a
+// pointer and refuses a copy command whose range leaves it (hipErrorInvalidValue), so the staged copies of the _host entries take it
+// through a pageable buffer of their own: HostStage.
+static bool host_straddles(const void* p, size_t bytes) {
+  std::lock_guard<std::mutex> lk(g_pin_mu);
+  auto it = g_pins.upper_bound(static_cast<const char*>(p));
+  if (it == g_pins.begin()) return false;
+  --it;
+  const char* end = it->first + it->second;
+  return static_cast<const char*>(p) < end && static_cast<const char*>(p) + bytes > end;
+}
+
+// The host side of a _host entry's two staged copies: the caller's buffers, or pageable stand-ins for those that straddle (lives until the
+// entry has synchronised; `finish` then hands the result over).
+struct HostStage {
+  const float* in;
+  float* out;
+  float* caller_out;
+  size_t bytes;
+  std::vector<float> tmp_in, tmp_out;
+  HostStage(const float* host_in, float* host_out, size_t n_bytes) : in(host_in), out(host_out), caller_out(host_out), bytes(n_bytes) {
+    if (host_straddles(host_in, bytes)) {
+      tmp_in.assign(host_in, host_in + bytes / sizeof(float));
+      in = tmp_in.data();
+    }
+    if (host_straddles(host_out, bytes)) {
+      tmp_out.resize(bytes / sizeof(float));
+      out = tmp_out.data();
+    }
+  }
+  void finish() const {
+    if (out != caller_out) std::memcpy(caller_out, out, bytes);
+  }
+};
 
 // The B mask bytes of a _host entry, copied to the handle's device buffer on the library's stream (in front of the work that reads them).
 static int upload_active(Engine* e, const unsigned char* active) {
@@ -118,12 +155,14 @@ static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, 
     HIP_TRY(hipStreamSynchronize(e->stream));
     return NUTLS_OK;
   }
-  HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyHostToDevice, e->stream));
+  HostStage hs(mag_in, mag_out, bytes);
+  HIP_TRY(hipMemcpyAsync(e->io_in, hs.in, bytes, hipMemcpyHostToDevice, e->stream));
   int rc = step_impl(h, e->io_in, e->io_out, d_act, e->stream);
   if (rc) return rc;
   if (active) note_active(e, active);
-  HIP_TRY(hipMemcpyAsync(mag_out, e->io_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(hs.out, e->io_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  hs.finish();
   return NUTLS_OK;
 }
 
@@ -249,11 +288,13 @@ static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pc
     HIP_TRY(hipStreamSynchronize(e->stream));
     return NUTLS_OK;
   }
-  HIP_TRY(hipMemcpyAsync(e->fe_pcm_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  HostStage hs(pcm_in, pcm_out, bytes);
+  HIP_TRY(hipMemcpyAsync(e->fe_pcm_in, hs.in, bytes, hipMemcpyHostToDevice, e->stream));
   if ((rc = enhance_hop_impl(h, e->fe_pcm_in, e->fe_pcm_out, d_act, dc_mode, e->stream))) return rc;
   if (active) note_active(e, active);
-  HIP_TRY(hipMemcpyAsync(pcm_out, e->fe_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(hs.out, e->fe_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  hs.finish();
   return NUTLS_OK;
 }
 

@@ -11,7 +11,10 @@ the float32 oracle's distance from it is what decides whether a family is fit to
 The baseline half: every family starts from ``synthetic_weights("baseline", SEED, bias_std=0.1, affine_jitter=0.1)``, is stored with
 ``write_blob(..., int8_convs=True)`` (the form the fused kernel takes) and runs BASE_FRAMES = 37 frames: block 6 of every dilated-dense
 block taps the frame 32 steps back, so its history is live for the last 5 frames only, and at 37 every history ring of depth >= 2 sits at
-a non-zero phase (37 & (d - 1) = 1, 1, 5, 5, 5 for d = 2, 4, 8, 16, 32)."""
+a non-zero phase (37 & (d - 1) = 1, 1, 5, 5, 5 for d = 2, 4, 8, 16, 32).
+
+The section "large offsets" near the end: the index maps, the eight-utterance call sequence and the references of the handles whose arena
+offsets pass 2^31 and 2^32 (tests/test_large_offsets.py, tests/test_gpu_large_offsets.py)."""
 import functools
 
 import numpy as np
@@ -326,7 +329,7 @@ BLOCK_SETS = {2: {"blocks": (17, 1, 9), "ragged": {0: (6, 17), 2: (9, 4)}},
 
 
 def block_set_inputs(utterances):
-    return block_inputs() if utterances == 2 else block3_inputs()
+    return block_inputs() if utterances == 2 else block3_inputs() if utterances == 3 else block8_inputs()
 
 
 def block_set_families(utterances):
@@ -442,11 +445,180 @@ def baseline_continuation(family):
 
 
 @functools.lru_cache(maxsize=None)
-def block_reference(family, dtype=torch.float64, utterances=2):
+def block_reference(family, dtype=torch.float64, utterances=2, ctfa_mode="frame"):
     """The block-mode inputs (two utterances, or the three of `block3_inputs`), frame by frame through the oracle (utterances as the
-    batch); all states are kept after the frames of `block_keep_frames`."""
+    batch); all states are kept after the frames of `block_keep_frames`.  ``utterances=8``: the call sequence of the large-offset set
+    (`Block8Reference`; ``ctfa_mode`` is for that set alone)."""
+    if utterances == 8:
+        return Block8Reference(family, dtype, ctfa_mode)
+    if ctfa_mode != "frame":
+        raise ValueError("the two- and three-utterance sets run the frame-wise CTFA")
     x = block_set_inputs(utterances)
     return _oracle(container(family), np.ascontiguousarray(x.transpose(1, 0, 2)), dtype, trace=False, keep=block_keep_frames(utterances))
+
+
+# ---- large offsets (tests/test_large_offsets.py, tests/test_gpu_large_offsets.py) -----------------------------------------------------------
+# Every kernel addresses a stream's (a frame's) slice as arena + row * sstride.  NUTLS_STRIDE_ALIGN (floats; read by `arena_commit` when a
+# handle is created) rounds the slice stride up to a multiple of its value: with 2^24 floats every slice is 2^26 bytes, whatever the layout
+# (the largest slice, an offline row, is about 2.6 MB), and row r starts r x 2^26 bytes into the arena.
+STRIDE_ALIGN = 1 << 24          # floats
+ROW_BYTES = 4 * STRIDE_ALIGN
+# what an offset can outgrow -> the first row that starts at or beyond it
+THRESHOLD_ROWS = {"2^31 bytes": (1 << 31) // ROW_BYTES, "2^32 bytes": (1 << 32) // ROW_BYTES,
+                  "2^31 floats": (4 << 31) // ROW_BYTES, "2^32 floats": (4 << 32) // ROW_BYTES}
+# the streaming handles: (variant, streams per workgroup as requested from `NutlsEngine` (None: the library's choice), B, the plan that runs)
+LARGE_HANDLES = (("lstm", 1, 264, 1), ("lstm", 2, 300, 2), ("lstm", 4, 264, 4), ("baseline", None, 264, 1))
+LARGE_FOURTH = (5, 70, 200)          # rows that carry base stream 3, beside row B - 1
+# the tensors whose row B - 1 is edited through `state_set`, and read whole ([B, ...]) through `state_get`: a conv-input state and a small one
+LARGE_EDITED = {"lstm": ("msfe6_ee_prev1", "state_h"), "baseline": ("msfe6_ee_prev1", "ddb_prev3")}
+
+
+def large_index_map(B):
+    """idx[r]: the base stream that row r of a B-row handle carries.  (r // 32) % 3: the rows 32, 64, 128 and 256 below r (1, 2, 4, 8 groups of
+    32: 1, 2, 1, 2 modulo 3) carry another stream, so a row whose offset lost its bits above 2^31 or 2^32, of bytes or of floats, lands on
+    different data -- never on a replica that hides the mistake.  Base stream 3 rides on the rows of LARGE_FOURTH and on row B - 1."""
+    idx = (np.arange(B) // 32) % 3
+    idx[list(LARGE_FOURTH) + [B - 1]] = 3
+    return idx
+
+
+def large_map_ok(idx):
+    """The condition on an index map: idx[r] != idx[r - T] for every threshold distance T and every r >= T."""
+    return all(not np.any(idx[T:] == idx[:-T]) for T in THRESHOLD_ROWS.values() if T < len(idx))
+
+
+def large_sample_rows(B):
+    """The rows whose whole state is read: both sides of every threshold, the first and the last."""
+    return sorted({0, B - 1} | {T - 1 for T in THRESHOLD_ROWS.values()} | set(THRESHOLD_ROWS.values()))
+
+
+def large_held_rows(B):
+    """The rows the masked step holds."""
+    return (255, 256, B - 1)
+
+
+class LargeContinuation:
+    """What follows the base run on a large streaming handle, through the float64 oracle on five rows: base streams 0 .. 3 as they go on,
+    and row 4 = the handle's row B - 1 (base stream 3).
+      step 1: row 4 starts from the states of stream 3 with the tensors of LARGE_EDITED replaced by ``edits`` (float32 values; the handle is
+              given the same through `state_set`); every row takes frame ``extra[0]`` of its stream.
+      step 2: row 4 starts from nothing (`reset(B - 1)`) and takes frame 0 of stream 3; the others take ``extra[1]``.
+      step 3: the others take ``extra[2]`` (the handle holds three rows here, row B - 1 among them).
+    ``steps[i]``: a `Run` of one frame, ``out [1, 5, 256]`` and ``state``."""
+
+    def __init__(self, variant):
+        start = reference("plain", variant=variant)
+        names = state_names(variant)
+        x = baseline_streams() if variant == "baseline" else base_streams()
+        self.extra = (BASE_FRAMES, BASE_FRAMES + 1, BASE_FRAMES + 2) if variant == "baseline" else (1, 2, 3)
+        a, b = LARGE_EDITED[variant]
+        self.edits = {a: np.float32(start.state[a][0]), b: np.float32(0.5 * start.state[b][3] + 0.25)}
+        state = {n: np.concatenate([start.state[n], start.state[n][3:4]]) for n in names}
+        for n, v in self.edits.items():
+            state[n][4] = v
+        blob, self.steps = container("plain", variant=variant), []
+        for i, f in enumerate(self.extra):
+            frame = np.concatenate([x[f], x[0 if i == 1 else f][3:4]])[None]
+            if i == 1:
+                for n in names:
+                    state[n][4] = 0.0
+            run = _oracle(blob, frame, torch.float64, trace=False, variant=variant, state=state)
+            self.steps.append(run)
+            state = {n: np.array(run.state[n]) for n in names}
+
+
+@functools.lru_cache(maxsize=None)
+def large_continuation(variant="lstm"):
+    return LargeContinuation(variant)
+
+
+# The offline set: eight utterances in a handle of max_frames = 32 (8 x 33 = 264 arena rows; utterance u's carried slot is row 33 u, its
+# frame t row 33 u + 1 + t: utterance 7's frames 25 .. 32 start beyond 2^32 floats).  Per call one count per utterance: a uniform block of
+# 32, a ragged block of width 32 (an utterance held, one frame, a full row next to short ones), a uniform block of 7; then utterance
+# BLOCK8_RESET starts anew and a uniform block of BLOCK8_TAIL follows.  Every utterance takes its own stream's frames in order.
+BLOCK8_MAX = 32
+BLOCK8_CALLS = ((32,) * 8, (32, 0, 1, 17, 32, 5, 31, 32), (7,) * 8)
+BLOCK8_RESET = 7
+BLOCK8_TAIL = 5
+BLOCK8_FRAMES = 32 + 32 + 7 + BLOCK8_TAIL
+BLOCK8_MODES = ("frame", "causal32")
+
+
+def block8_calls():
+    """All four calls: the three of BLOCK8_CALLS and the block behind the reset."""
+    return BLOCK8_CALLS + ((BLOCK8_TAIL,) * 8,)
+
+
+def block8_starts():
+    """starts[k][u]: the frames of its stream that utterance u has taken before call k (k = 0 .. 4; 4: at the end)."""
+    starts = [[0] * 8]
+    for counts in block8_calls():
+        starts.append([a + c for a, c in zip(starts[-1], counts)])
+    return starts
+
+
+@functools.lru_cache(maxsize=None)
+def block8_inputs():
+    """[8, BLOCK8_FRAMES, 256]: the recipes of `block_inputs` and `block3_inputs` (noise; silence, a single bin at 50, then 1e-20; noise under
+    a swinging gain) and five more streams of noise, each of its own draw and level, one of them falling to 1e-20 after 20 frames."""
+    n = BLOCK8_FRAMES
+    noise = lambda u: np.abs(np.random.default_rng([SEED + 9, u]).standard_normal((n, 256)))
+    x = np.zeros((8, n, 256), np.float32)
+    x[0] = 0.25 * noise(0)
+    x[1, 2:40, 40] = 50.0
+    x[1, 40:] = 1e-20
+    x[2] = 0.25 * noise(2) * np.float32(0.51 + 0.49 * np.cos(1.3 * np.arange(n)))[:, None]
+    x[3] = 0.05 * noise(3)
+    x[4] = 1.0 * noise(4)
+    x[5] = 0.25 * noise(5)
+    x[5, 20:] = 1e-20
+    x[6] = 0.5 * noise(6)
+    x[7] = 0.25 * noise(7)
+    x.setflags(write=False)
+    return x
+
+
+class Block8Reference:
+    """The call sequence of the offline set through the oracle, utterances as the batch, frame by frame: ``out(k, u) [count, 256]``, the
+    output rows of utterance u in call k, and ``state(k, u)[name]``, its states after that call (after its last frame so far: a held
+    utterance keeps what it had).  Utterance BLOCK8_RESET's last call comes from a second oracle that starts from nothing."""
+
+    def __init__(self, family, dtype, ctfa_mode):
+        x, blob = block8_inputs(), container(family)
+        self.starts, self.calls = block8_starts(), block8_calls()
+        names = state_names()
+        ends = {}          # frame -> [(call, utterance)]: whose state to keep behind that frame
+        for k, counts in enumerate(self.calls):
+            for u in range(8):
+                if not (k == 3 and u == BLOCK8_RESET):
+                    ends.setdefault(self.starts[k + 1][u] - 1, []).append((k, u))
+        self._out, self._state = {}, {}
+
+        def run(frames, rows, ends):
+            ref = NutlsRef(parse_blob(blob), batch=len(rows), dtype=dtype, variant="lstm", ctfa_mode=ctfa_mode)
+            outs = []
+            for f in range(frames.shape[0]):
+                outs.append(ref.step(frames[f]).numpy().astype(np.float64))
+                for k, u in ends.get(f, ()):
+                    self._state[k, u] = {n: ref.state[n][rows.index(u)].numpy().astype(np.float64) for n in names}
+            return np.stack(outs)
+
+        main = run(np.ascontiguousarray(x.transpose(1, 0, 2)), list(range(8)), ends)
+        a = self.starts[3][BLOCK8_RESET]
+        fresh = run(np.ascontiguousarray(x[BLOCK8_RESET:BLOCK8_RESET + 1, a:a + BLOCK8_TAIL].transpose(1, 0, 2)), [BLOCK8_RESET],
+                    {BLOCK8_TAIL - 1: [(3, BLOCK8_RESET)]})
+        for k, counts in enumerate(self.calls):
+            for u, c in enumerate(counts):
+                a = self.starts[k][u]
+                self._out[k, u] = fresh[:, 0] if (k == 3 and u == BLOCK8_RESET) else main[a:a + c, u]
+        for a in list(self._out.values()) + [v for d in self._state.values() for v in d.values()]:
+            a.setflags(write=False)
+
+    def out(self, call, utterance):
+        return self._out[call, utterance]
+
+    def state(self, call, utterance):
+        return self._state[call, utterance]
 
 
 # ---- measures ----------------------------------------------------------------------------------------------------------------------
