@@ -334,7 +334,40 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  *     int16 output is that float, rounded to nearest even and saturated: bit for bit what NUTLS_PCM_F32 returns, then quantised.
  *   - In place: the _pcm device entries read pcm_in in their decode launch only, which has run before the encode launch writes pcm_out, so
  *     pcm_in == pcm_out (the same base pointer; no other overlap) is allowed, with the upper band on as with it off: u waits in a library buffer.
- *   - Cost: README, "PCM gateway".  Out of scope: a gain that follows the model's suppression (the "follow" mode of band-split suppressors).
+ *   - Cost: README, "PCM gateway".
+ *   - Follow (nutls_set_pcm_upper_follow(h, 1)): the gain of nutls_set_pcm_upper_band becomes the CEILING of a gain that follows the suppression
+ *     the model applied below 8 kHz, the "follow" mode of band-split suppressors: in a pause the hiss above 8 kHz goes where the noise below it
+ *     went, in speech the upper band comes back at the ceiling.  Hops are counted per row (a stream or an utterance): t runs over the row's real
+ *     hops since its last reset or format, gain or follow switch; hops before the first have energy 0; held ticks and hops behind a ragged count
+ *     do not exist for this count.  d_t = the 256 decoded 16 kHz samples of hop t (what the decode half writes); y_t = the 256 samples the encode
+ *     half is handed for hop t (in the _pcm entries the model's output, which lags d by one hop).  All arithmetic is fp32, every operation
+ *     rounded on its own (no contraction; / and sqrt correctly rounded), in this one order:
+ *       E2(v)  : s[i] = v[i] * v[i]; for h = 128, 64, ..., 1: s[i] = s[i] + s[i + h], i < h; the result is s[0]
+ *       a_t = E2(d_t)            b_t = E2(y_t)
+ *       A_t = ((a_{t-1} + a_{t-2}) + a_{t-3}) + a_{t-4}      W = NUTLS_PCM_FOLLOW_HOPS = 4 hops; shifted by the model's one-hop lag
+ *       B_t = ((b_t + b_{t-1}) + b_{t-2}) + b_{t-3}
+ *       g_t = gain * fminf(sqrt(B_t / fmaxf(A_t, 0x1p-100f)), 1)
+ *       delta_t = g_t - g_{t-1};  w[n] = float(n + 1) * float32(1.0 / S);  gamma_t[n] = fmaf(delta_t, w[n], g_{t-1})     n = 0 .. S - 1
+ *       out[n] = fmaf(gamma_t[n], u[n - S], z[n])                                         in place of fmaf(gain, u[n - S], z[n]) above
+ *     gamma is a linear ramp across the hop that ends at g_t (w[S - 1] is exactly 1 for S = 512 and 768): no step at a hop edge.  g_{t-1} is
+ *     the same formula on the windows one hop earlier, not a recurrence: every g is a function of at most 5 values of a and 5 of b, so every
+ *     output sample is the same sequence of operations wherever a hop, block or tick boundary falls, and a and b are the same bits on the same
+ *     samples (one energy code for both halves).  Where y_t = c d_{t-1} with c a power of two, g_t = gain * min(c, 1) exactly, and from the
+ *     second such hop on out is bit for bit the fixed gain's.  Errors, to first order: A_t and B_t carry 12 roundings on non-negative terms,
+ *     |g32 - g| <= 20 * 2^-24 g, |gamma32 - gamma| <= 24 * 2^-24 gain, and out is within the bound above taken at the ceiling plus
+ *     24 * 2^-24 gain (|x[n - 2 K q - S]| + q sum |p| (sum |p| |x|)).
+ *       . Enabling follow while the gain is 0 is NUTLS_ERR_ARG and changes nothing -- that is every 8000 / 16000 Hz handle.  Setting the value the
+ *         handle already has is a no-op that touches nothing.  A real change synchronises and zeroes every row's resampler histories,
+ *         upper-band and follow state, as a gain change does.  nutls_set_pcm_upper_band(h, 0) and nutls_set_pcm_format turn follow OFF; a
+ *         change from one gain other than 0 to another keeps it (and zeroes the state, as ever).  nutls_pcm_upper_follow reads it back.
+ *       . Follow off, every entry launches exactly the kernels it launches without this call -- same bits.  On, every _pcm entry honours it in the
+ *         two launches it already makes: hop, _active, _host, _host_active, block, block _host, the _ragged entries; hop fusion on or off makes
+ *         no difference.  So do the halves, signatures unchanged: the decode half records a of what it decodes, the encode half uses the a of the
+ *         handle's LAST DECODED hop or block -- the contract it has for u.
+ *       . State per row, allocated when follow is first enabled: the last 5 a, the last 4 b and the last g.  It obeys the rules of the last hop
+ *         of u: nutls_reset zeroes it, a held row's is not touched, a count k carries it from hop k - 1, k = 0 holds it.
+ *       . nutls_pcm_follow_gain(h, gains, n): HOST gains[rows] = g of each row's last real encoded hop (0 after a reset); synchronises the
+ *         device.  NUTLS_ERR_ARG with follow off or n other than the handle's rows (streams / utterances).
  *
  * State: per stream (utterance) and direction the library keeps the filter's last 2 K q input samples, outside the signature's tensors.
  * nutls_reset(h, b) zeroes stream b's (-1: everybody's).  A held stream (active[b] == 0) keeps it as it is -- neither kernel touches it -- and
@@ -353,12 +386,16 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * _pcm_ragged entries at the end of this section.  Zero-copy reads of pinned PCM stay out of scope: the _host entries copy. */
 #define NUTLS_PCM_F32 0   /* float32, unit scale (what nutls_enhance_hop takes) */
 #define NUTLS_PCM_S16 1   /* int16, little endian; 32768 = 1.0 */
-int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);   /* also turns the upper band off (gain 0) */
+int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);   /* also turns the upper band off (gain 0), and follow with it */
 /* "Upper band" above.  gain in 0 .. 1, 0 = off (the default); NaN, a gain outside 0 .. 1, or a gain other than 0 at 8000 / 16000 Hz:
  * NUTLS_ERR_ARG, nothing changes.  Synchronises and zeroes every stream's resampler histories and upper-band state, unless the gain is the
  * one the handle already has.  nutls_set_pcm_format resets it to 0: call this after it. */
 int nutls_set_pcm_upper_band(nutls_handle* h, float gain);
 int nutls_pcm_upper_band(nutls_handle* h, float* gain);      /* the gain in force */
+#define NUTLS_PCM_FOLLOW_HOPS 4   /* hops of the two energy windows of follow ("Upper band" above) */
+int nutls_set_pcm_upper_follow(nutls_handle* h, int enable);   /* gain of nutls_set_pcm_upper_band becomes the CEILING of a gain that follows the model */
+int nutls_pcm_upper_follow(nutls_handle* h, int* enable);
+int nutls_pcm_follow_gain(nutls_handle* h, float* gains, int n);  /* HOST [rows]: g of each row's last real encoded hop; synchronous; 0 after reset */
 int nutls_pcm_hop_samples(nutls_handle* h);     /* S = 256 * rate / 16000: 128, 256, 512, 768 */
 int nutls_pcm_delay_samples(nutls_handle* h);   /* delay of the two rate conversions together, in samples at the caller's rate */
 int nutls_pcm_filter_taps(int rate_hz);         /* host only, no handle: 2 K q + 1; 1 for 16000; -1 for an unsupported rate */

@@ -6,6 +6,7 @@
 // The _pcm_ragged block entries do the same around nutls_enhance_block_ragged, with the per-utterance hop counts handed to both kernels.
 // Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): with a gain other than 0 decode_launch / encode_launch start the kernels that also
 // form and add the band above 8 kHz -- every entry below goes through those two, so every entry honours the gain; with 0 nothing here differs.
+// Follow (nutls_set_pcm_upper_follow): the same two launches start the kernels whose gain follows the model; off, nothing here differs.
 // The kernels: pcm.hip.
 #include <cstdint>
 
@@ -58,8 +59,21 @@ int upper_init(Engine* e) {
   return NUTLS_OK;
 }
 
-// Row idx's (< 0: every row's) resampler histories and upper-band state, where they exist.  (up_u is not state: the encode half reads only what
-// the decode half of the same hop or block wrote there.)
+// Follow's buffers (nutls_set_pcm_upper_follow), allocated when follow is first enabled -- after upper_init.
+int follow_init(Engine* e) {
+  PcmState& st = e->pcm;
+  if (st.follow_ready) return NUTLS_OK;
+  const size_t rows = static_cast<size_t>(st.rows);
+  int rc;
+  if ((rc = dev_alloc_once(e, rows * max_hops(e), &st.fo_a, true)) || (rc = dev_alloc_once(e, rows * kPcmFollowCarry, &st.fo_carry[0], true)) ||
+      (rc = dev_alloc_once(e, rows * kPcmFollowCarry, &st.fo_carry[1], true)))
+    return rc;
+  st.follow_ready = true;
+  return NUTLS_OK;
+}
+
+// Row idx's (< 0: every row's) resampler histories, upper-band and follow state, where they exist.  (up_u and fo_a are not state: the encode half reads only
+// what the decode half of the same hop or block wrote there.)
 int zero_histories(Engine* e, int idx) {
   PcmState& st = e->pcm;
   if (!st.ready) return NUTLS_OK;
@@ -75,16 +89,24 @@ int zero_histories(Engine* e, int idx) {
     if (int rc = zero(st.up_ctx[i], kPcmUpCtx)) return rc;
     if (int rc = zero(st.up_last[i], kPcmMaxHop)) return rc;
   }
+  if (!st.follow_ready) return NUTLS_OK;
+  for (int i = 0; i < 2; ++i)
+    if (int rc = zero(st.fo_carry[i], kPcmFollowCarry)) return rc;
   return NUTLS_OK;
 }
 
 // One launch of a half.  A block call (offline handle) flips the history buffers; a hop call (streaming handle) works in place on buffer 0.
 // counts: the DEVICE counts of a ragged block or null (the flip is the whole handle's: the kernel carries a held row's history across).
 // With the upper band on (a gain other than 0) the launch is the kernel that also forms / adds it; its carried state flips with the histories.
+// With follow on top it is the kernel whose gain follows the model; follow's carried state is the encode half's and flips with enc_par.
 int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
-  if (st.upper != 0.f) {
+  if (st.upper != 0.f && st.follow) {
+    const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
+    const PcmFollow fo = {st.fo_a, nullptr, nullptr};
+    HIP_TRY(launch_pcm_decode_follow(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, fo, s));
+  } else if (st.upper != 0.f) {
     const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
     HIP_TRY(launch_pcm_decode_upper(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
   } else {
@@ -97,7 +119,11 @@ int decode_launch(Engine* e, const void* in, float* out, const unsigned char* ac
 int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
   const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
-  if (st.upper != 0.f) {
+  if (st.upper != 0.f && st.follow) {
+    const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
+    const PcmFollow fo = {st.fo_a, st.fo_carry[par], st.fo_carry[nxt]};
+    HIP_TRY(launch_pcm_encode_follow(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, fo, s));
+  } else if (st.upper != 0.f) {
     const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
     HIP_TRY(launch_pcm_encode_upper(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
   } else {
@@ -243,6 +269,7 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
     e->pcm.rate = rate_hz;
     e->pcm.fmt = sample_format;
     e->pcm.upper = 0.f;
+    e->pcm.follow = false;
     return NUTLS_OK;
   }
   HIP_TRY(hipSetDevice(e->device));
@@ -250,6 +277,7 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
   e->pcm.rate = rate_hz;
   e->pcm.fmt = sample_format;
   e->pcm.upper = 0.f;                   // a new format starts anew: the upper band is off until nutls_set_pcm_upper_band
+  e->pcm.follow = false;                // ... and with it follow
   if (!e->pcm.ready) {
     if (int rc = pcm_init(e)) return rc;      // (uploads the taps, zeroes the histories)
   } else {
@@ -275,6 +303,7 @@ int nutls_set_pcm_upper_band(nutls_handle* h, float gain) {
     if (int rc = upper_init(e)) return rc;
   if (int rc = zero_histories(e, -1)) return rc;      // like a format switch: every stream starts anew, resamplers and upper band
   e->pcm.upper = gain == 0.f ? 0.f : gain;
+  if (gain == 0.f) e->pcm.follow = false;      // nothing is left to follow with; another gain other than 0 keeps it
   HIP_TRY(hipDeviceSynchronize());
   return NUTLS_OK;
 }
@@ -282,6 +311,42 @@ int nutls_set_pcm_upper_band(nutls_handle* h, float gain) {
 int nutls_pcm_upper_band(nutls_handle* h, float* gain) {
   if (!h || !gain) return fail(NUTLS_ERR_ARG, "nutls_pcm_upper_band: null pointer");
   *gain = h->eng.pcm.upper;
+  return NUTLS_OK;
+}
+
+int nutls_set_pcm_upper_follow(nutls_handle* h, int enable) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_upper_follow: null handle");
+  Engine* e = &h->eng;
+  const bool on = enable != 0;
+  if (on == e->pcm.follow) return NUTLS_OK;      // nothing is touched
+  if (on && e->pcm.upper == 0.f)
+    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_upper_follow: the upper band's gain is 0 (rate " + std::to_string(e->pcm.rate) +
+                                   " Hz): there is no ceiling to follow under (nutls_set_pcm_upper_band with a gain other than 0 first, at 32000 or 48000 Hz)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // queued conversions still read the state that changes below
+  if (on)
+    if (int rc = follow_init(e)) return rc;      // (a gain other than 0 is in force: pcm_init and upper_init have run)
+  if (int rc = zero_histories(e, -1)) return rc;      // like a gain change: every stream starts anew
+  e->pcm.follow = on;
+  HIP_TRY(hipDeviceSynchronize());
+  return NUTLS_OK;
+}
+
+int nutls_pcm_upper_follow(nutls_handle* h, int* enable) {
+  if (!h || !enable) return fail(NUTLS_ERR_ARG, "nutls_pcm_upper_follow: null pointer");
+  *enable = h->eng.pcm.follow ? 1 : 0;
+  return NUTLS_OK;
+}
+
+int nutls_pcm_follow_gain(nutls_handle* h, float* gains, int n) {
+  if (!h || !gains) return fail(NUTLS_ERR_ARG, "nutls_pcm_follow_gain: null pointer");
+  Engine* e = &h->eng;
+  if (!e->pcm.follow) return fail(NUTLS_ERR_ARG, "nutls_pcm_follow_gain: follow is off (nutls_set_pcm_upper_follow)");
+  if (n != e->pcm.rows) return fail(NUTLS_ERR_ARG, "nutls_pcm_follow_gain: n must be the handle's rows, " + std::to_string(e->pcm.rows));
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // the encode launches queued on the callers' streams have written what is read here
+  HIP_TRY(hipMemcpy2D(gains, sizeof(float), e->pcm.fo_carry[e->pcm.enc_par] + kPcmFollowGainAt, kPcmFollowCarry * sizeof(float), sizeof(float),
+                      static_cast<size_t>(n), hipMemcpyDeviceToHost));
   return NUTLS_OK;
 }
 

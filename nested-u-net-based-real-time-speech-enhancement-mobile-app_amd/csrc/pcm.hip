@@ -25,6 +25,8 @@
 //   out[n] = fmaf(gain, u[n - S], z[n])                                                                    (one FMA)
 // The longest path of an output sample has 2 K q + 2 K + 4 roundings (d, c, u, out).  +49 FMAs per caller sample in the decode, and the 2 K
 // decoded samples of context computed again by every hop of a block but its first (+19 % of the decode chains); the encode adds one FMA.
+// Follow (nutls_set_pcm_upper_follow): the gain of out[n] follows the model, gamma_t[n] of nutls.h -- two more kernels again (pcm_hop<..., UPPER,
+// FOLLOW>), in the same two launches; one energy code for both halves (pcm_e2), every g a function of 5 a and 5 b, so one workgroup per (row, hop).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -124,6 +126,50 @@ __device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
   for (int i = tid; i < count / 8; i += kThreads) reinterpret_cast<s16x8*>(dst)[i] = z;
 }
 
+// ---- follow: the upper band's gain follows the model (nutls.h, "Upper band", follow) ------------------------------------------------------------
+// Everything here is fp32 in one fixed order, each operation rounded on its own: the pragma keeps the compiler from contracting a product
+// into a sum, and / and __builtin_sqrtf are the correctly rounded ones (this file is built without fast-math).
+// E2 of nutls.h for `slots` hops at once, by all 256 threads: s[256 j + i] = sample i of hop j on entry (thread i has written its own), the
+// energy of hop j in s[256 j] on return (behind a barrier).  The ONE energy code of both halves: a of the decode half and b of the encode half
+// are the same bits on the same samples.
+__device__ __forceinline__ void pcm_e2(float* s, int slots, int tid) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < slots; ++j) {
+    const float v = s[256 * j + tid];
+    s[256 * j + tid] = v * v;
+  }
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if (tid < h)
+      for (int j = 0; j < slots; ++j) s[256 * j + tid] = s[256 * j + tid] + s[256 * j + tid + h];
+    __syncthreads();
+  }
+}
+
+// g of a hop from its two windows, oldest energy last: a1 .. a4 = a_{t-1} .. a_{t-4}, b0 .. b3 = b_t .. b_{t-3}
+__device__ __forceinline__ float pcm_follow_gain(float gain, float a1, float a2, float a3, float a4, float b0, float b1, float b2, float b3) {
+#pragma clang fp contract(off)
+  const float A = ((a1 + a2) + a3) + a4;
+  const float Bw = ((b0 + b1) + b2) + b3;
+  const float r = __builtin_sqrtf(Bw / fmaxf(A, 0x1p-100f));
+  return gain * fminf(r, 1.f);
+}
+
+// The samples pcm_e2 works on, in LDS: one array per size, the same one wherever a kernel asks for it
+template <int N>
+__device__ __forceinline__ float* pcm_follow_lds() {
+  __shared__ float s_e[N];
+  return s_e;
+}
+
+// gamma of the hop's caller sample n (S per hop): the linear ramp from g_prev (reached by the hop in front) to g_prev + delta
+template <int S>
+__device__ __forceinline__ float pcm_follow_ramp(float g_prev, float delta, int n) {
+#pragma clang fp contract(off)
+  const float w = static_cast<float>(n + 1) * static_cast<float>(1.0 / S);
+  return fmaf(delta, w, g_prev);
+}
+
 // ---- one hop of one row: NIN samples in, NIN / Q (DOWN) or NIN * Q (UP) out --------------------------------------------------------------------
 // UPPER (nutls_set_pcm_upper_band; rates above 16 kHz, so DOWN is the decode half and UP the encode half; ub: pcm.hpp, PcmUpper):
 //   decode: after the hop's decoded samples d, u[n] = fmaf(-Q, c[n], x[n - 2 K Q]) for the hop's S = NIN caller samples, c[n] = pcm_up_chain over
@@ -132,9 +178,14 @@ __device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
 //           same bits -- from 2 K Q more input samples of the row (the decoded hop in front of it is another workgroup's of the same launch);
 //   encode: out[n] = fmaf(gain, u'[n], z[n]), z the sample without the upper band, u' the u of the hop in front: ub.u's for a later hop of a
 //           block, the carried one (ub.carry_in) for the first.  The workgroup of the row's last real hop carries that hop's u on.
-template <int Q, bool UP, int NIN, typename TI, typename TO, bool UPPER = false>
+// FOLLOW (nutls_set_pcm_upper_follow; with UPPER only; fo: pcm.hpp, PcmFollow): gain becomes the sample's gamma.
+//   decode: a = pcm_e2 of the hop's 256 decoded samples, to fo.a[row, t] (one lane, one store);
+//   encode: b of the hop and of the 4 in front of it by pcm_e2 -- the earlier hops of the call read again from the input row, those in front of the
+//           call from the carried state, like their a (fo.a inside the call) --, lane 0 forms g_t and g_{t-1}, each from its own two windows, and
+//           every lane its samples' gamma = the ramp between them.  The workgroup of the row's last real hop carries the last 5 a, 4 b and g on.
+template <int Q, bool UP, int NIN, typename TI, typename TO, bool UPPER = false, bool FOLLOW = false>
 __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                        const int* counts, int n_hops, const PcmUpper ub = PcmUpper{}) {
+                                        const int* counts, int n_hops, const PcmUpper ub = PcmUpper{}, const PcmFollow fo = PcmFollow{}) {
   constexpr int K = Rate<Q>::k;
   constexpr int HIST = UP ? 2 * K : 2 * K * Q;      // samples of left context
   constexpr int NOUT = UP ? NIN * Q : NIN / Q;
@@ -144,6 +195,7 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
   constexpr int CARRY = DEC_UPPER ? kPcmUpCtx : kPcmMaxHop, NCARRY = DEC_UPPER ? YPRE : NOUT;      // a row's carried upper-band state: stride, floats in use
   static_assert(HIST <= kPcmMaxHist && HIST <= NIN && NIN <= kPcmMaxHop && NOUT <= kPcmMaxHop, "staging sizes");
   static_assert(HIST % 8 == 0 && NIN % 8 == 0 && NOUT % 8 == 0, "16-byte accesses");
+  static_assert(!FOLLOW || (UPPER && (UP ? NIN : NOUT) == kThreads && kThreads == 256), "follow: one lane per 16 kHz sample of the hop");
   static_assert(!UPPER || (Q > 1 && YPRE == (DEC_UPPER ? kPcmUpCtx : 0) && YPRE + NOUT <= kPcmMaxHop && XPRE + HIST <= NIN && XPRE % 8 == 0 && YPRE % 8 == 0), "upper band: staging sizes");
   __shared__ __attribute__((aligned(16))) float s_x[(DEC_UPPER ? kPcmMaxHist : 0) + kPcmMaxHist + kPcmMaxHop];
   __shared__ __attribute__((aligned(16))) float s_y[kPcmMaxHop];
@@ -168,6 +220,9 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
           f32x4* const uto = reinterpret_cast<f32x4*>(ub.carry_out + static_cast<size_t>(row) * CARRY);
           for (int i = tid; i < NCARRY / 4; i += kThreads) uto[i] = ufrom[i];
         }
+        if constexpr (FOLLOW && UP) {      // and its follow state
+          if (tid < kPcmFollowCarry) fo.carry_out[static_cast<size_t>(row) * kPcmFollowCarry + tid] = fo.carry_in[static_cast<size_t>(row) * kPcmFollowCarry + tid];
+        }
       }
     }
     return;
@@ -183,6 +238,10 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
     }
   }
   stage_in(src, xs + HIST, NIN, tid);
+  if constexpr (FOLLOW && UP) {      // slot i of s_e: the 256 samples of hop t - i (a hop in front of the call: zeros, its b is the carried one)
+    float* const s_e = pcm_follow_lds<(kPcmFollowHops + 1) * 256>();
+    for (int i = 0; i <= kPcmFollowHops; ++i) s_e[i * 256 + tid] = t - i >= 0 ? src[tid - i * 256] : 0.f;
+  }
   __syncthreads();
   if constexpr (HIST > 0) {
     // the history the next call starts from: the row's last real hop's.  hist_out may be hist_in only where this workgroup is also the one that read it (n_hops == 1)
@@ -198,11 +257,51 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
     for (int n = tid; n < NIN; n += kThreads) xs[n] = fmaf(-static_cast<float>(Q), pcm_up_chain<Q>(s_p, s_y, n), xs[n]);
     __syncthreads();
     stage_out(xs, ub.u + (static_cast<size_t>(row) * n_hops + t) * NIN, NIN, tid);
+    if constexpr (FOLLOW) {      // (s_y: complete behind the barriers above, only read from here on)
+      float* const s_e = pcm_follow_lds<256>();
+      s_e[tid] = s_y[YPRE + tid];
+      pcm_e2(s_e, 1, tid);
+      if (tid == 0) fo.a[static_cast<size_t>(row) * n_hops + t] = s_e[0];
+    }
     return;
   }
   if constexpr (ENC_UPPER) {
     const float* const before = t > 0 ? ub.u + (static_cast<size_t>(row) * n_hops + t - 1) * NOUT : ub.carry_in + static_cast<size_t>(row) * CARRY;
-    for (int n = tid; n < NOUT; n += kThreads) s_y[n] = fmaf(ub.gain, before[n], pcm_fir<Q, UP>(s_p, xs, n));
+    if constexpr (FOLLOW) {
+      __shared__ float s_g[2];      // g_{t-1} and g_t - g_{t-1}
+      float* const s_e = pcm_follow_lds<(kPcmFollowHops + 1) * 256>();
+      pcm_e2(s_e, kPcmFollowHops + 1, tid);
+      if (tid == 0) {
+        const float* const ca = fo.carry_in + static_cast<size_t>(row) * kPcmFollowCarry;
+        const float* const ar = fo.a + static_cast<size_t>(row) * n_hops;
+        float a[kPcmFollowHops + 1], b[kPcmFollowHops + 1];      // a[i] = a_{t-1-i}, b[i] = b_{t-i}: inside the call or carried (hop -1 - j of the call: ca[j], ca[5 + j])
+#pragma unroll
+        for (int i = 0; i <= kPcmFollowHops; ++i) {
+          a[i] = t - 1 - i >= 0 ? ar[t - 1 - i] : ca[i - t];
+          b[i] = t - i >= 0 ? s_e[i * 256] : ca[kPcmFollowHops + i - t];
+        }
+        const float a_t = ar[t];
+        const float g_now = pcm_follow_gain(ub.gain, a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]);
+        const float g_prev = pcm_follow_gain(ub.gain, a[1], a[2], a[3], a[4], b[1], b[2], b[3], b[4]);
+        s_g[0] = g_prev;
+        s_g[1] = g_now - g_prev;
+        if (t == k - 1) {      // (every carried value this lane needs is read above: carry_out may be carry_in where n_hops == 1)
+          float* const co = fo.carry_out + static_cast<size_t>(row) * kPcmFollowCarry;
+          co[0] = a_t;
+#pragma unroll
+          for (int i = 0; i < kPcmFollowHops; ++i) {
+            co[1 + i] = a[i];
+            co[kPcmFollowHops + 1 + i] = b[i];
+          }
+          co[kPcmFollowGainAt] = g_now;
+        }
+      }
+      __syncthreads();
+      const float g_prev = s_g[0], delta = s_g[1];
+      for (int n = tid; n < NOUT; n += kThreads) s_y[n] = fmaf(pcm_follow_ramp<NOUT>(g_prev, delta, n), before[n], pcm_fir<Q, UP>(s_p, xs, n));
+    } else {
+      for (int n = tid; n < NOUT; n += kThreads) s_y[n] = fmaf(ub.gain, before[n], pcm_fir<Q, UP>(s_p, xs, n));
+    }
   } else {
     for (int n = tid; n < NOUT; n += kThreads) s_y[n] = pcm_fir<Q, UP>(s_p, xs, n);
   }
@@ -238,6 +337,19 @@ template <int Q, typename TO>
 __global__ __launch_bounds__(kThreads) void pcm_encode_upper_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
                                                                     const unsigned char* active, const int* counts, int n_hops, PcmUpper ub) {
   pcm_hop<Q, true, 256, float, TO, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub);
+}
+
+// The two with the upper band's gain following the model
+template <int Q, typename TI>
+__global__ __launch_bounds__(kThreads) void pcm_decode_follow_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
+                                                                     const unsigned char* active, const int* counts, int n_hops, PcmUpper ub, PcmFollow fo) {
+  pcm_hop<Q, false, 256 * Q, TI, float, true, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo);
+}
+
+template <int Q, typename TO>
+__global__ __launch_bounds__(kThreads) void pcm_encode_follow_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
+                                                                     const unsigned char* active, const int* counts, int n_hops, PcmUpper ub, PcmFollow fo) {
+  pcm_hop<Q, true, 256, float, TO, true, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo);
 }
 
 template <int Q, bool UP, typename T>
@@ -360,6 +472,42 @@ hipError_t launch_pcm_encode_upper(const float* in, void* out, const float* taps
     return hipErrorInvalidValue;
   }
 #undef NUTLS_PCM_ENCODE_UPPER
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm_decode_follow(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s) {
+  const dim3 grid(n_hops, rows), block(kThreads);
+#define NUTLS_PCM_DECODE_FOLLOW(Q, T) \
+  hipLaunchKernelGGL((pcm_decode_follow_kernel<Q, T>), grid, block, 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo)
+  if (rate_hz == 32000) {
+    if (s16) NUTLS_PCM_DECODE_FOLLOW(2, short);
+    else NUTLS_PCM_DECODE_FOLLOW(2, float);
+  } else if (rate_hz == 48000) {
+    if (s16) NUTLS_PCM_DECODE_FOLLOW(3, short);
+    else NUTLS_PCM_DECODE_FOLLOW(3, float);
+  } else {
+    return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_DECODE_FOLLOW
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm_encode_follow(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s) {
+  const dim3 grid(n_hops, rows), block(kThreads);
+#define NUTLS_PCM_ENCODE_FOLLOW(Q, T) \
+  hipLaunchKernelGGL((pcm_encode_follow_kernel<Q, T>), grid, block, 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out, active, counts, n_hops, ub, fo)
+  if (rate_hz == 32000) {
+    if (s16) NUTLS_PCM_ENCODE_FOLLOW(2, short);
+    else NUTLS_PCM_ENCODE_FOLLOW(2, float);
+  } else if (rate_hz == 48000) {
+    if (s16) NUTLS_PCM_ENCODE_FOLLOW(3, short);
+    else NUTLS_PCM_ENCODE_FOLLOW(3, float);
+  } else {
+    return hipErrorInvalidValue;
+  }
+#undef NUTLS_PCM_ENCODE_FOLLOW
   return hipGetLastError();
 }
 

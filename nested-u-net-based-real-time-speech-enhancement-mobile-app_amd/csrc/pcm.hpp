@@ -17,6 +17,9 @@ constexpr int kPcmMaxQ = 3;
 constexpr int kPcmMaxHist = 2 * kPcmK * kPcmMaxQ;      // floats of history per row and direction (the longest: 48 kHz decode)
 constexpr int kPcmMaxHop = 256 * kPcmMaxQ;             // samples of a hop at the highest rate
 constexpr int kPcmUpCtx = 2 * kPcmK;                   // upper band: decoded samples of left context the decode half carries per row
+constexpr int kPcmFollowHops = 4;                      // follow: hops of the two energy windows (NUTLS_PCM_FOLLOW_HOPS)
+constexpr int kPcmFollowCarry = 16;                    // follow: floats a row carries -- [0 .. 4] the last 5 a, [5 .. 8] the last 4 b (newest first), [9] the last g
+constexpr int kPcmFollowGainAt = 2 * kPcmFollowHops + 1;      // where g sits in them
 
 // q of a supported rate (8000, 16000, 32000, 48000), else 0
 int pcm_ratio(int rate_hz);
@@ -46,6 +49,12 @@ struct PcmState {
   float* up_ctx[2] = {nullptr, nullptr};       // [rows][kPcmUpCtx] the last 2 K DECODED samples (the left context of E(D(x))); flips with dec_par
   float* up_last[2] = {nullptr, nullptr};      // [rows][kPcmMaxHop] u of the last real hop the encode half has seen the decode of; flips with enc_par
   float* up_u = nullptr;               // [rows, n_hops * S] u of the last decoded hop / block (written by the decode half, read by the encode half)
+  // Follow (nutls_set_pcm_upper_follow): the gain above becomes the ceiling of one that follows sqrt(energy handed to the encode half / energy
+  // decoded) over kPcmFollowHops hops.  Allocated when follow is first enabled; zeroed with the histories above.
+  bool follow = false;                 // on: the launches are the upper band's kernels with FOLLOW
+  bool follow_ready = false;           // the buffers below exist
+  float* fo_a = nullptr;               // [rows, n_hops] a = E2 of each hop of the last decoded hop / block (the contract of up_u)
+  float* fo_carry[2] = {nullptr, nullptr};     // [rows][kPcmFollowCarry] as of the last real hop the encode half has seen; flips with enc_par (the rules of up_last)
 };
 
 // What a launch with the upper band gets on top (by value).  Decode: u = where the hops' u goes, [rows, n_hops * S]; carry_in / carry_out =
@@ -54,6 +63,14 @@ struct PcmState {
 struct PcmUpper {
   float gain;
   float* u;
+  const float* carry_in;
+  float* carry_out;
+};
+
+// What a launch with follow gets on top of PcmUpper (by value).  Decode: a = where the hops' energies go, [rows, n_hops]; the rest is not used.
+// Encode: a = the same buffer, read; carry_in / carry_out = [rows][kPcmFollowCarry], following the rules of hist_in and hist_out.
+struct PcmFollow {
+  float* a;
   const float* carry_in;
   float* carry_out;
 };
@@ -73,5 +90,10 @@ hipError_t launch_pcm_decode_upper(const void* in, float* out, const float* taps
                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s);
 hipError_t launch_pcm_encode_upper(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s);
+// The same two with the upper band's gain following the model: again other kernels, none of the above is touched.
+hipError_t launch_pcm_decode_follow(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s);
+hipError_t launch_pcm_encode_follow(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
+                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s);
 
 }  // namespace nutls

@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "nutls_enhance_block_pcm", "nutls_enhance_block_pcm_host", "nutls_pcm_decode_block", "nutls_pcm_encode_block",
     "nutls_enhance_block_pcm_ragged", "nutls_enhance_block_pcm_ragged_host", "nutls_pcm_decode_block_ragged", "nutls_pcm_encode_block_ragged",
     "nutls_set_pcm_upper_band", "nutls_pcm_upper_band",
+    "nutls_set_pcm_upper_follow", "nutls_pcm_upper_follow", "nutls_pcm_follow_gain",
 )
 
 
@@ -164,6 +165,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not dev_lib or hasattr(lib, "nutls_set_pcm_upper_band"):
         lib.nutls_set_pcm_upper_band.argtypes = [c.c_void_p, c.c_float]
         lib.nutls_pcm_upper_band.argtypes = [c.c_void_p, fp]
+    if not dev_lib or hasattr(lib, "nutls_set_pcm_upper_follow"):
+        lib.nutls_set_pcm_upper_follow.argtypes = [c.c_void_p, c.c_int]
+        lib.nutls_pcm_upper_follow.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
+        lib.nutls_pcm_follow_gain.argtypes = [c.c_void_p, fp, c.c_int]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -268,6 +273,29 @@ class _PcmFormat:
         g = ctypes.c_float(0.0)
         _check(self._lib, self._lib.nutls_pcm_upper_band(self._h, ctypes.byref(g)))
         return float(g.value)
+
+    def set_pcm_upper_follow(self, enable: bool) -> None:
+        """The upper band's gain FOLLOWS the model (``nutls_set_pcm_upper_follow``): per hop it is the gain of ``set_pcm_upper_band`` -- now
+        the ceiling -- times ``min(1, sqrt(energy of the model's output / energy of its input))`` over the last 4 hops, ramped linearly
+        across the hop, so a pause loses its hiss above 8 kHz as it loses its noise below.  May be called between any two hops: a change
+        restarts every stream's resampler history, upper-band and follow state from zeros (nothing happens when ``enable`` is the value
+        in force).  ``set_pcm_format`` and ``set_pcm_upper_band(0)`` turn it off.  ``ValueError``: enabling while the gain is 0, which
+        includes every 8000 / 16000 Hz handle."""
+        _check(self._lib, self._lib.nutls_set_pcm_upper_follow(self._h, 1 if enable else 0))
+
+    @property
+    def pcm_upper_follow(self) -> bool:
+        """Whether the upper band's gain follows the model (``nutls_pcm_upper_follow``)."""
+        on = ctypes.c_int(0)
+        _check(self._lib, self._lib.nutls_pcm_upper_follow(self._h, ctypes.byref(on)))
+        return bool(on.value)
+
+    def pcm_follow_gain(self) -> np.ndarray:
+        """``[rows]`` float32 (streams of a streaming handle, utterances of an offline one): the followed gain of each row's last real
+        encoded hop, 0.0 after a reset (``nutls_pcm_follow_gain``; synchronises).  ``ValueError`` while follow is off."""
+        g = np.zeros(getattr(self, "utterances", None) or self.batch, np.float32)
+        _check(self._lib, self._lib.nutls_pcm_follow_gain(self._h, _fptr(g), len(g)))
+        return g
 
     @property
     def pcm_hop_samples(self) -> int:
@@ -1111,14 +1139,15 @@ class NutlsOffline(_PcmFormat):
             out[:, a * S:b * S] = block(np.ascontiguousarray(padded[:, a * S:b * S]))
         return out[:, lag:lag + n]
 
-    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge", upper_gain: float = 0.0) -> np.ndarray:
+    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge", upper_gain: float = 0.0, upper_follow: bool = False) -> np.ndarray:
         """A whole recording in its own format: ``wave [N]`` (one utterance) or ``[utterances, N]``, int16 or float32 numpy array of any
         length at ``rate`` (8000, 16000, 32000, 48000) -> the enhanced recording of the same shape and dtype, ALIGNED with the input:
         sample i of the result belongs to ``wave[i]`` (the input is padded with zeros to whole hops plus the total lag, one hop plus
         ``pcm_delay_samples``, and that lag is dropped from the front).  Sets the handle's format (``set_pcm_format``: the rate conversion
         starts from a zero history); the model state carries on from earlier calls until :meth:`reset`.  ``upper_gain``: the gain of the band
         above 8 kHz of a 32 or 48 kHz recording, passed around the model (``set_pcm_upper_band``, set after the format); 0.0: the result is
-        band-limited to 8 kHz."""
+        band-limited to 8 kHz.  ``upper_follow``: that gain is the ceiling of one that follows the model's suppression
+        (``set_pcm_upper_follow``, set after the gain)."""
         self._dc(dc_mode)
         x = np.asarray(wave)
         if x.dtype.name not in self._PCM_FORMATS:
@@ -1130,6 +1159,7 @@ class NutlsOffline(_PcmFormat):
             raise ValueError("wave must be [%sN], got %s" % ("%d," % self.utterances if self.utterances > 1 else "", np.shape(wave)))
         self.set_pcm_format(rate, x.dtype)
         self.set_pcm_upper_band(upper_gain)
+        self.set_pcm_upper_follow(upper_follow)
         lag = self.pcm_hop_samples + self.pcm_delay_samples
         out = self._wave_through_blocks(x, lag, lambda blk: self.enhance_block_pcm_host(blk, None, dc_mode))
         return out if batched else out[0]
@@ -1192,7 +1222,7 @@ class NutlsOffline(_PcmFormat):
         ``rate`` (8000, 16000, 32000, 48000): the recordings are in the callers' format, int16 or float32 arrays at that rate, all of one
         dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
         handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format, which turns the upper band
-        (``set_pcm_upper_band``) off: the results are band-limited to 8 kHz."""
+        (``set_pcm_upper_band``) and with it its following gain (``set_pcm_upper_follow``) off: the results are band-limited to 8 kHz."""
         dc = self._dc(dc_mode)
         if rate is not None:
             return self._enhance_many_pcm(waves, dc, rate)
