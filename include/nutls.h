@@ -149,7 +149,9 @@ int nutls_enhance_hop_host(nutls_handle* h, const float* pcm_in, float* pcm_out,
 int nutls_enhance_hop_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode, void* stream);
 int nutls_enhance_hop_host_active(nutls_handle* h, const float* pcm_in, float* pcm_out, const unsigned char* active, int dc_mode);
 /* The two halves on their own (testing, custom models): analysis of one hop into the library's mag_in buffer
- * (+ phase kept inside), synthesis of one hop from the library's mag_out buffer.  Device pointers. */
+ * (+ phase kept inside), synthesis of one hop from the library's mag_out buffer.  Device pointers.
+ * nutls_istft_hop honours the attenuation limit ("Attenuation limit" below): while a row's limit is not 0 it also reads the library's
+ * mag_in buffer, as the last nutls_stft_hop left it, as the noisy rows of the frame. */
 int nutls_stft_hop(nutls_handle* h, const float* pcm_in, void* stream);
 int nutls_istft_hop(nutls_handle* h, float* pcm_out, int dc_mode, void* stream);
 
@@ -437,6 +439,40 @@ int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pc
 int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode);
 int nutls_pcm_decode_block_ragged(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, const int* hops, void* stream);
 int nutls_pcm_encode_block_ragged(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, const int* hops, void* stream);
+
+/* ---- Attenuation limit: a per-row cap on how much noise is removed ------------------------------------------------------
+ * Every waveform entry returns the model's full suppression by default.  With a limit l in 0 .. 1 on a row (a stream of a streaming handle,
+ * an utterance of an offline one) the synthesis mixes, per bin 1..256 of every frame, the noisy magnitude x of that frame (as the analysis
+ * wrote it) with the model's magnitude e of the same frame, on the frame's own phase:
+ *     m' = fma(l, x, c * e),   c = (float)(1.0 - (double)l) formed once on the host,
+ * the product c * e and the fma rounded separately.  Both magnitudes share the phasors and the synthesis is linear, so the samples are
+ * (1 - l) * enhanced + l * noisy, aligned, with no delay line and no extra launch; since e >= 0 no bin is attenuated below l * x, i.e. by more
+ * than -20 log10(l) dB.  The DC rule (dc_mode) applies to m' as it applied to e.
+ *   - Exact ends: l = 0 (the default) gives m' = e bit for bit, l = 1 gives m' = x bit for bit (the input through analysis and synthesis).
+ *   - A setting, not stream state: it survives nutls_reset, nutls_set_pcm_format and mode switches.  The kernels read it from a per-row
+ *     device array, so a change holds from the next call.  A row held by an `active` mask or behind a ragged count behaves as before: a zero
+ *     hop, its overlap tail kept, no input row read.
+ *   - Kernels: while EVERY row of a handle is 0 every entry launches exactly the kernels it launches without this section -- same bits.  As
+ *     soon as one row is not 0 the synthesis of every launch is its mix twin, and the rows at 0 go through it with (l, c) = (0, 1).
+ *   - Who honours it: nutls_istft_hop (noisy rows = the library's mag_in buffer as the last nutls_stft_hop left it) and with it every
+ *     nutls_enhance_hop* entry -- device, _host, _active, _pcm*; nutls_enhance_block, _ragged, their _host forms and the _pcm* block entries
+ *     (noisy rows = the library's mag_in buffer); nutls_istft_block_mix.  Who does not: nutls_istft_block[_ragged], which have no noisy rows
+ *     (nutls_stft_block wrote them to the caller's buffer) and stay exactly as they are, and the magnitude entries nutls_step* and
+ *     nutls_process_block* -- a caller who holds both rows mixes them itself.
+ *   - Hop fusion: the one-launch hop builds have no mix.  nutls_set_atten_limit with a value other than 0 on a handle in hop fusion, and
+ *     nutls_set_hop_fusion(h, nonzero) while a row's limit is not 0, are NUTLS_ERR_ARG and change nothing; an all-zero set is accepted.
+ *   - PCM gateway: decode and encode sit around the plain hop or block and get the limit through it.  The upper band's follow mode
+ *     (nutls_set_pcm_upper_follow) then follows the LIMITED suppression: its B_t is the energy of what the encode half is handed.
+ * nutls_set_atten_limit(h, limit, n): limit is a HOST array of n = the handle's rows (streams / utterances) floats; NULL sets every row to 0.
+ * A value outside 0 .. 1, a NaN or a wrong n is NUTLS_ERR_ARG (nutls_last_error names the entry) and changes nothing.  A CONTROL-PLANE call,
+ * like nutls_offline_set_ctfa_mode: it synchronises the device, then writes the per-row (l, c) array -- not for the audio path's inner loop.
+ * nutls_atten_limit(h, limit, n): HOST limit[rows] = the l in force. */
+int nutls_set_atten_limit(nutls_handle* h, const float* limit, int n);
+int nutls_atten_limit(nutls_handle* h, float* limit, int n);
+/* The synthesis half of the waveform block mode with the noisy rows in the caller's hands: est, noisy DEVICE [utterances, n_hops, 256] (noisy
+ * as nutls_stft_block[_ragged] wrote it), hops DEVICE [utterances] counts as in nutls_istft_block_ragged or NULL for the uniform block.
+ * Otherwise nutls_istft_block[_ragged]; with every limit 0 it launches their kernels and never reads noisy. */
+int nutls_istft_block_mix(nutls_handle* h, const float* est, const float* noisy, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
 
 /* Library-owned device staging buffers [B,256]; stepping on them avoids the D2D copies and lets
  * the captured hipGraph run with no per-call parameter update. */

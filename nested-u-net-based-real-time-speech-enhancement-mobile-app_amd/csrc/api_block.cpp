@@ -116,11 +116,16 @@ static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_h
   return NUTLS_OK;
 }
 
-static int istft_block_launch(Engine* e, const float* mag, float* pcm_out, int n_hops, int dc_mode, hipStream_t s, const int* hops = nullptr) {
+// noisy: the magnitudes of the same block (the enhance entries: io_in; nutls_istft_block_mix: the caller's) or null (the stand-alone half, which
+// has none).  With noisy rows and an attenuation limit in force (nutls_set_atten_limit) the mix kernel runs for the whole launch.
+static int istft_block_launch(Engine* e, const float* mag, const float* noisy, float* pcm_out, int n_hops, int dc_mode, hipStream_t s, const int* hops = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
   if (n_hops != e->fb_hops) return fail(NUTLS_ERR_ARG, "nutls_istft_block: n_hops differs from the block the phasors inside the handle belong to (nutls_stft_block first)");
-  if (hops) HIP_TRY(launch_istft_block_ragged(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
+  if (noisy && e->atten_on)
+    HIP_TRY(launch_istft_block_mix(mag, noisy, e->d_atten, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
+                                   dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
+  else if (hops) HIP_TRY(launch_istft_block_ragged(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
                                               dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
   else HIP_TRY(launch_istft_block(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
                                   dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->outt, n_hops, s));
@@ -342,7 +347,7 @@ int nutls_stft_block(nutls_handle* h, const float* pcm_in, float* mag, int n_hop
 int nutls_istft_block(nutls_handle* h, const float* mag, float* pcm_out, int n_hops, int dc_mode, void* stream) {
   if (int rc = block_args(h, mag && pcm_out, n_hops, "nutls_istft_block")) return rc;
   if (int rc = block_dc(dc_mode, "nutls_istft_block")) return rc;
-  return istft_block_launch(&h->eng, mag, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream));
+  return istft_block_launch(&h->eng, mag, nullptr, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream));
 }
 
 int nutls_enhance_block(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, int dc_mode, void* stream) {
@@ -354,7 +359,7 @@ int nutls_enhance_block(nutls_handle* h, const float* pcm_in, float* pcm_out, in
   // analysis and have joined it again when nutls_process_block returns
   if (int rc = stft_block_launch(e, pcm_in, e->io_in, n_hops, s)) return rc;
   if (int rc = nutls_process_block(h, e->io_in, e->io_out, n_hops, stream)) return rc;
-  return istft_block_launch(e, e->io_out, pcm_out, n_hops, dc_mode, s);
+  return istft_block_launch(e, e->io_out, e->io_in, pcm_out, n_hops, dc_mode, s);
 }
 
 // ---- ragged waveform blocks: hops [utterances] of int, utterance u has hops[u] real hops in a block whose row stride is n_hops (nutls.h) ----
@@ -368,7 +373,14 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
   if (!hops) return nutls_istft_block(h, mag, pcm_out, n_hops, dc_mode, stream);
   if (int rc = block_args(h, mag && pcm_out, n_hops, "nutls_istft_block_ragged")) return rc;
   if (int rc = block_dc(dc_mode, "nutls_istft_block_ragged")) return rc;
-  return istft_block_launch(&h->eng, mag, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream), hops);
+  return istft_block_launch(&h->eng, mag, nullptr, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream), hops);
+}
+
+// the synthesis half with the noisy rows in the caller's hands (nutls_stft_block wrote them there): honours the attenuation limit; hops: DEVICE or null
+int nutls_istft_block_mix(nutls_handle* h, const float* est, const float* noisy, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  if (int rc = block_args(h, est && noisy && pcm_out, n_hops, "nutls_istft_block_mix")) return rc;
+  if (int rc = block_dc(dc_mode, "nutls_istft_block_mix")) return rc;
+  return istft_block_launch(&h->eng, est, noisy, pcm_out, n_hops, dc_mode, static_cast<hipStream_t>(stream), hops);
 }
 
 int nutls_enhance_block_ragged(nutls_handle* h, const float* pcm_in, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
@@ -380,7 +392,7 @@ int nutls_enhance_block_ragged(nutls_handle* h, const float* pcm_in, float* pcm_
   // the analysis writes zero magnitudes behind the counts and the synthesis reads no row there: the block runs in place on the library's buffers
   if (int rc = stft_block_launch(e, pcm_in, e->io_in, n_hops, s, hops)) return rc;
   if (int rc = process_block_impl(h, e->io_in, e->io_out, n_hops, hops, true, stream, "nutls_enhance_block_ragged")) return rc;
-  return istft_block_launch(e, e->io_out, pcm_out, n_hops, dc_mode, s, hops);
+  return istft_block_launch(e, e->io_out, e->io_in, pcm_out, n_hops, dc_mode, s, hops);
 }
 
 // ---- the _host entries: one body ------------------------------------------------------------------------------------------------------

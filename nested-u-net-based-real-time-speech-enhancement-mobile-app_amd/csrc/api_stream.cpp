@@ -200,8 +200,14 @@ static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const un
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
-  HIP_TRY(launch_istft_hop(e->io_out, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->B,
-                           static_cast<hipStream_t>(stream), active));
+  // an attenuation limit in force (nutls_set_atten_limit): the mix kernel for the whole launch, the noisy rows being io_in as the analysis left them
+  // (an offline handle's limits are per utterance, not per arena slot: they belong to its block entries)
+  if (e->atten_on && !e->offline)
+    HIP_TRY(launch_istft_hop_mix(e->io_out, e->io_in, e->d_atten, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0,
+                                 e->B, static_cast<hipStream_t>(stream), active));
+  else
+    HIP_TRY(launch_istft_hop(e->io_out, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->B,
+                             static_cast<hipStream_t>(stream), active));
   return NUTLS_OK;
 }
 
@@ -216,6 +222,8 @@ int nutls_set_hop_fusion(nutls_handle* h, int enable) {
   Engine* e = &h->eng;
   if (!enable) { e->hop_fusion = false; return NUTLS_OK; }
   if (int rc = check_hop_fusion(e, "nutls_set_hop_fusion")) return rc;
+  if (e->atten_on)
+    return fail(NUTLS_ERR_ARG, "nutls_set_hop_fusion: not while an attenuation limit is in force (the single-launch hop has no mix) -- nutls_set_atten_limit(h, NULL, n) first");
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_init(e)) return rc;
   HIP_TRY(e->fz_plan->set_attributes_hop());

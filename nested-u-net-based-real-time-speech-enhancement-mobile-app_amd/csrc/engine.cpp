@@ -1170,6 +1170,48 @@ int nutls_set_ctfa_mode(nutls_handle* h, int mode) {
   return NUTLS_OK;
 }
 
+/* Attenuation limit (nutls.h): per row the pair (l, c = 1 - l) the mix kernels of the two syntheses read.  A control-plane call: everything is
+ * checked first -- a refused call changes nothing --, then the device is synchronised and the array written.  While every row is 0 the
+ * syntheses launch the kernels they always launched; the array is allocated by the first set that is not all zero. */
+int nutls_set_atten_limit(nutls_handle* h, const float* limit, int n) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_atten_limit: null handle");
+  Engine* e = &h->eng;
+  const int rows = e->offline ? e->outt : e->B;
+  if (n != rows) return fail(NUTLS_ERR_ARG, "nutls_set_atten_limit: n = " + std::to_string(n) + ", the handle has " + std::to_string(rows) + " rows (streams / utterances)");
+  bool on = false;
+  for (int r = 0; limit && r < rows; ++r) {
+    if (!(limit[r] >= 0.f && limit[r] <= 1.f))      // (a NaN fails both comparisons)
+      return fail(NUTLS_ERR_ARG, "nutls_set_atten_limit: limit " + std::to_string(limit[r]) + " of row " + std::to_string(r) + " is outside 0 .. 1");
+    on = on || limit[r] != 0.f;
+  }
+  if (on)
+    if (int rc = refuse_in_hop_fusion(e, "nutls_set_atten_limit")) return rc;      // (the one-launch hop builds have no mix)
+  if (!on && !e->d_atten) return NUTLS_OK;                                         // all zero on a handle that never had a limit: nothing to write
+  std::vector<float> lc(static_cast<size_t>(rows) * 2);
+  for (int r = 0; r < rows; ++r) {
+    const float l = limit ? limit[r] + 0.f : 0.f;                                  // (-0 becomes +0)
+    lc[2 * static_cast<size_t>(r)] = l;
+    lc[2 * static_cast<size_t>(r) + 1] = static_cast<float>(1.0 - static_cast<double>(l));
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = dev_alloc_once(e, lc.size(), &e->d_atten, false)) return rc;
+  HIP_TRY(hipMemcpy(e->d_atten, lc.data(), lc.size() * sizeof(float), hipMemcpyHostToDevice));
+  e->atten.resize(static_cast<size_t>(rows));
+  for (int r = 0; r < rows; ++r) e->atten[static_cast<size_t>(r)] = lc[2 * static_cast<size_t>(r)];
+  e->atten_on = on;
+  return NUTLS_OK;
+}
+
+int nutls_atten_limit(nutls_handle* h, float* limit, int n) {
+  if (!h || !limit) return fail(NUTLS_ERR_ARG, "nutls_atten_limit: null pointer");
+  const Engine* e = &h->eng;
+  const int rows = e->offline ? e->outt : e->B;
+  if (n != rows) return fail(NUTLS_ERR_ARG, "nutls_atten_limit: n = " + std::to_string(n) + ", the handle has " + std::to_string(rows) + " rows (streams / utterances)");
+  for (int r = 0; r < rows; ++r) limit[r] = e->atten.empty() ? 0.f : e->atten[static_cast<size_t>(r)];
+  return NUTLS_OK;
+}
+
 int nutls_destroy(nutls_handle* h) {
   if (!h) return NUTLS_OK;
   (void)hipSetDevice(h->eng.device);

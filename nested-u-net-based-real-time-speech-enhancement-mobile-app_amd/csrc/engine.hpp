@@ -189,6 +189,12 @@ struct Engine {
   int ochunks = 0;                      // 0 = chosen from the block length
   int* d_counts = nullptr;              // [outt] ints: device copy of the counts of the _host entries of the ragged block calls (nutls_process_block_ragged_host)
   std::vector<int> ogroup;              // launch index of plan_off -> group (a group ends with an LSTM)
+  // ---- attenuation limit ----------------------------------------------------------------------
+  // nutls_set_atten_limit: per row (stream / utterance) the limit l in force; a setting, not stream state -- no reset touches it.  d_atten [rows]
+  // (l, c) pairs, allocated by the first set; atten_on = some row's l is not 0, and only then do the syntheses run their mix kernels.
+  std::vector<float> atten;
+  float* d_atten = nullptr;
+  bool atten_on = false;
   // ---- PCM gateway ---------------------------------------------------------------------------
   PcmState pcm;          // the callers' sample rate and type (nutls_set_pcm_format) and the resampler histories of the _pcm entries
 

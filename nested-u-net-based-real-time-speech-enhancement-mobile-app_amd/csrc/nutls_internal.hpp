@@ -227,6 +227,13 @@ hipError_t launch_stft_block(const float* pcm, const float* tail_in, float* tail
                              int U, int n_hops, hipStream_t s);
 hipError_t launch_istft_block(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
                               float* pcm_out, int dc_edge, int U, int n_hops, hipStream_t s);
+// The two syntheses with an attenuation limit (nutls_set_atten_limit): noisy = the magnitudes of the same frames ([B][256] / [U][n_hops][256]),
+// lim = one (l, c) float pair per stream / utterance, c = 1 - l formed on the host; each bin is synthesised from fma(l, noisy, c * est).
+// hops: DEVICE per-utterance counts as in launch_istft_block_ragged, or null for the uniform block.
+hipError_t launch_istft_hop_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                                float* ola, float* pcm_out, int dc_edge, int B, hipStream_t s, const unsigned char* active = nullptr);
+hipError_t launch_istft_block_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                                  const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s);
 // (Rounds 1-3 kept a third kernel family here: a persistent plan-interpreter kernel, megakernel.hip, execution mode 2 -- retired in
 //  round 4: the fused kernel is the one-launch path, the per-layer kernels below are the cross-check and the block mode.)
 

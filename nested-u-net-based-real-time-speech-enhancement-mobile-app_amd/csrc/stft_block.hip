@@ -273,6 +273,73 @@ __global__ __launch_bounds__(64 * kWaves) void istft_block_ragged_kernel(const f
   }
 }
 
+// ---- the two synthesis kernels with an attenuation limit (nutls_set_atten_limit / nutls_istft_block_mix) ----
+// noisy [U][n_hops][256]: the magnitudes of the same frames as the analysis wrote them; lim [U] = (l, c) of each utterance, loaded once per wave.
+// Every frame is synthesised from m' = fma(l, x, c * e) (synthesise_frame_mix); runs, tiles and carry are those of the kernels above, RAGGED
+// their ragged twin: the noisy row of the redundant frame in front of a run is read again like its estimate, no row behind a count is read.
+// Kernels of their own, so that the four above stay the code they were.
+template <bool RAGGED>
+__global__ __launch_bounds__(64 * kWaves) void istft_block_mix_kernel(const float* __restrict__ est, const float* __restrict__ noisy,
+                                                                      const float2* __restrict__ lim, const float2* __restrict__ ph,
+                                                                      const float* __restrict__ inv_win, const float2* __restrict__ tw,
+                                                                      const float* __restrict__ ola_in, float* __restrict__ ola_out,
+                                                                      float* __restrict__ pcm_out, int dc_edge, int n_hops,
+                                                                      const int* __restrict__ hops) {
+  __shared__ float2 image[kWaves][kImage];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
+  const int o0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;      // this wave produces output hops [o0, o1)
+  if (o0 >= n_hops) return;
+  int o1 = min(o0 + kRun, n_hops);
+  const size_t row0 = static_cast<size_t>(u) * n_hops;
+  int last = n_hops;
+  if (RAGGED) {
+    last = min(max(hops[u], 0), n_hops);                                     // the carry is the second half of frame last - 1
+    for (int f = max(o0, last); f < o1; ++f) {
+      float2* orow = reinterpret_cast<float2*>(pcm_out + (row0 + f) * H);
+      orow[lane] = make_float2(0.f, 0.f);
+      orow[lane + 64] = make_float2(0.f, 0.f);
+    }
+    if (last == 0 && o0 == 0) {
+      const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
+      float2* to = reinterpret_cast<float2*>(ola_out + static_cast<size_t>(u) * H);
+      to[lane] = from[lane]; to[lane + 64] = from[lane + 64];
+    }
+    if (o0 >= last) return;
+    o1 = min(o1, last);
+  }
+  float2* buf = image[wave];
+  const Twiddles t = load_twiddles(tw, lane);
+  float2 iw[4], ws[4];
+  load_synthesis_regs(inv_win, tw, lane, iw, ws);
+  const float2 lc = lim[u];
+  float2 carry0 = make_float2(0.f, 0.f), carry1 = carry0;
+  if (o0 == 0) {
+    const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
+    carry0 = from[lane]; carry1 = from[lane + 64];
+  }
+  // frames o0 - 1 .. o1 - 1: the frame in front of the run only for its second half (the first run of a block has the carried one instead)
+#pragma unroll 1
+  for (int f = o0 > 0 ? o0 - 1 : 0; f < o1; ++f) {
+    const size_t row = row0 + f;
+    const float2* erow = reinterpret_cast<const float2*>(est + row * H);
+    const float2* xrow = reinterpret_cast<const float2*>(noisy + row * H);
+    const float2* prow = ph + row * (H + 1);
+    float2 v[4];
+    synthesise_frame_mix(erow, xrow, lc, prow, dc_edge, iw, ws, t, buf, lane, v);
+    if (f >= o0) {
+      float2* orow = reinterpret_cast<float2*>(pcm_out + row * H);
+      orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);
+      orow[lane + 64] = make_float2(carry1.x + v[1].x, carry1.y + v[1].y);
+    }
+    carry0 = v[2]; carry1 = v[3];
+    wave_sync();
+  }
+  if (o1 == last) {
+    float2* to = reinterpret_cast<float2*>(ola_out + static_cast<size_t>(u) * H);
+    to[lane] = carry0; to[lane + 64] = carry1;
+  }
+}
+
 std::vector<float> stft_block_twiddles() {
   std::vector<float> tw(static_cast<size_t>(2) * kTwEntries, 0.f);
   auto put = [&](int idx, double num, double den) {
@@ -316,6 +383,17 @@ hipError_t launch_istft_block_ragged(const float* est, const float* ph, const fl
                                      float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s) {
   hipLaunchKernelGGL(istft_block_ragged_kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
                      reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
+  return hipGetLastError();
+}
+
+hipError_t launch_istft_block_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                                  const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s) {
+  if (hops)
+    hipLaunchKernelGGL(istft_block_mix_kernel<true>, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, noisy, reinterpret_cast<const float2*>(lim),
+                       reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
+  else
+    hipLaunchKernelGGL(istft_block_mix_kernel<false>, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, noisy, reinterpret_cast<const float2*>(lim),
+                       reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
   return hipGetLastError();
 }
 

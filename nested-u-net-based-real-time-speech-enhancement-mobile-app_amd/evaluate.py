@@ -42,11 +42,12 @@ ENGINES = ("stream", "block")
 
 
 def evaluate_directory(directory: str, out_dir: Optional[str] = None, dc_mode: str = "edge", device: int = 0,
-                       engine: str = "stream") -> List[Dict[str, float]]:
+                       engine: str = "stream", atten_lim_db: Optional[float] = None) -> List[Dict[str, float]]:
     """All pairs of ``directory`` in ONE batched engine (one stream per clip; shorter clips are zero-padded to the
     longest and scored on their own length).  Returns one dict per clip; optionally writes ``<name>_enhanced.wav``.
     ``engine``: "stream" (default) -- a streaming engine fed hop by hop (:func:`stream_enhance.enhance_batch_on_device`);
-    "block" -- an offline handle fed blocks of up to 1024 hops (:func:`stream_enhance.enhance_utterances_offline`)."""
+    "block" -- an offline handle fed blocks of up to 1024 hops (:func:`stream_enhance.enhance_utterances_offline`).
+    ``atten_lim_db``: a cap in dB on the noise removed, for every clip (``set_atten_limit(db=...)``); None: the model's full suppression."""
     if engine not in ENGINES:
         raise ValueError("engine must be one of %s, got %r" % (list(ENGINES), engine))
     from .runner import NutlsEngine, NutlsOffline
@@ -63,12 +64,14 @@ def evaluate_directory(directory: str, out_dir: Optional[str] = None, dc_mode: s
         hops = (n_max - (SE.FRAME_LEN - SE.FRAME_STEP)) // SE.FRAME_STEP
         off = NutlsOffline(utterances=len(pairs), max_frames=max(1, min(1024, hops)), device=device)
         try:
+            off.set_atten_limit(db=atten_lim_db)
             enhanced = SE.enhance_utterances_offline(batch, off, dc_mode)
         finally:
             off.close()
     else:
         eng = NutlsEngine(batch=len(pairs), device=device)
         try:
+            eng.set_atten_limit(db=atten_lim_db)
             enhanced = SE.enhance_batch_on_device(batch, eng, dc_mode)
         finally:
             eng.close()

@@ -58,6 +58,7 @@ ABI_SYMBOLS = (
     "nutls_enhance_block_pcm_ragged", "nutls_enhance_block_pcm_ragged_host", "nutls_pcm_decode_block_ragged", "nutls_pcm_encode_block_ragged",
     "nutls_set_pcm_upper_band", "nutls_pcm_upper_band",
     "nutls_set_pcm_upper_follow", "nutls_pcm_upper_follow", "nutls_pcm_follow_gain",
+    "nutls_set_atten_limit", "nutls_atten_limit", "nutls_istft_block_mix",
 )
 
 
@@ -169,6 +170,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_set_pcm_upper_follow.argtypes = [c.c_void_p, c.c_int]
         lib.nutls_pcm_upper_follow.argtypes = [c.c_void_p, c.POINTER(c.c_int)]
         lib.nutls_pcm_follow_gain.argtypes = [c.c_void_p, fp, c.c_int]
+    if not dev_lib or hasattr(lib, "nutls_set_atten_limit"):
+        lib.nutls_set_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
+        lib.nutls_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
+        lib.nutls_istft_block_mix.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -243,8 +248,53 @@ def pcm_filter(rate: int, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
     return taps
 
 
+def atten_limit_from_db(db) -> np.float32:
+    """The attenuation limit ``l`` of a cap of ``db`` decibels on the noise removed: ``float32(10 ** (-db / 20))``; 0 dB -> 1 (nothing is
+    removed), ``None`` -> 0 (no cap: the model's full suppression).  ``ValueError``: a negative or NaN value."""
+    if db is None:
+        return np.float32(0.0)
+    d = float(db)
+    if not d >= 0.0:
+        raise ValueError("atten_lim_db must be >= 0 dB or None, got %r" % (db,))
+    return np.float32(10.0 ** (-d / 20.0))
+
+
 class _PcmFormat:
-    """The callers' sample format of a handle (``nutls_set_pcm_format``): shared by :class:`NutlsEngine` and :class:`NutlsOffline`."""
+    """The callers' sample format of a handle (``nutls_set_pcm_format``) and its attenuation limit (``nutls_set_atten_limit``): shared by
+    :class:`NutlsEngine` and :class:`NutlsOffline`."""
+
+    def _rows(self) -> int:
+        return getattr(self, "utterances", None) or self.batch
+
+    def set_atten_limit(self, limit=None, db=None) -> None:
+        """A cap on how much noise the waveform methods remove, per row (stream of a streaming handle, utterance of an offline one):
+        ``limit`` in [0, 1], a scalar for every row or one value per row -- every frame is synthesised from
+        ``limit * noisy + (1 - limit) * enhanced`` magnitudes on the frame's phase, so no bin is attenuated below ``limit`` times its input
+        (``nutls_set_atten_limit``).  ``db`` instead of ``limit``: the cap in decibels, scalar or per row, entries ``None`` for no cap
+        (:func:`atten_limit_from_db`).  Neither: every row back to 0, the model's full suppression, bit for bit as without this call.
+        A setting, not stream state: ``reset`` and ``set_pcm_format`` keep it; a change holds from the next call.  Synchronises the device.
+        ``ValueError``: a value outside [0, 1] or NaN, a wrong count, a negative ``db``, a value other than 0 while hop fusion is on --
+        nothing changes."""
+        if limit is not None and db is not None:
+            raise ValueError("give limit or db, not both")
+        rows = self._rows()
+        if db is not None:
+            seq = list(db) if isinstance(db, (list, tuple, np.ndarray)) else [db] * rows
+            vals = [atten_limit_from_db(d) for d in seq]
+        elif limit is not None:
+            vals = list(np.asarray(limit, dtype=np.float32).reshape(-1)) if np.ndim(limit) else [np.float32(limit)] * rows
+        else:
+            _check(self._lib, self._lib.nutls_set_atten_limit(self._h, None, rows))
+            return
+        a = np.ascontiguousarray(vals, dtype=np.float32)
+        _check(self._lib, self._lib.nutls_set_atten_limit(self._h, _fptr(a), len(a)))
+
+    @property
+    def atten_limit(self) -> np.ndarray:
+        """``[rows]`` float32: the attenuation limit in force for every stream / utterance (``nutls_atten_limit``); all 0 by default."""
+        a = np.zeros(self._rows(), np.float32)
+        _check(self._lib, self._lib.nutls_atten_limit(self._h, _fptr(a), len(a)))
+        return a
 
     _PCM_FORMATS = {"float32": 0, "int16": 1}
     pcm_rate, pcm_dtype = 16000, "float32"
@@ -1002,20 +1052,27 @@ class NutlsOffline(_PcmFormat):
             _check(self._lib, self._lib.nutls_stft_block_ragged(self._h, pcm.data_ptr(), out.data_ptr(), n, self._device_counts(hops, n, pcm, "hops"), stream))
         return out
 
-    def istft_block_device(self, mag, out=None, dc_mode: str = "edge", hops=None):
+    def istft_block_device(self, mag, out=None, dc_mode: str = "edge", hops=None, noisy=None):
         """Synthesis half only: magnitudes ``[n_hops,256]`` / ``[utterances,n_hops,256]`` with the phase of the last
         :meth:`stft_block_device` of the same ``n_hops`` -> PCM ``[n_hops*256]`` / ``[utterances,n_hops*256]``, overlap-added.
-        ``hops``: the counts that analysis was given (``nutls_istft_block_ragged``)."""
+        ``hops``: the counts that analysis was given (``nutls_istft_block_ragged``).  ``noisy``: the magnitudes that analysis returned, of
+        ``mag``'s shape -- the half then honours the attenuation limit (``set_atten_limit``; ``nutls_istft_block_mix``); without it the
+        limit is ignored."""
         import torch
         dc = self._dc(dc_mode)
         n = self._mag_hops(mag)
+        if noisy is not None and (self._mag_hops(noisy, "noisy") != n or noisy.shape != mag.shape or noisy.device != mag.device):
+            raise ValueError("noisy must have mag's shape and device")
         shape = tuple(mag.shape[:-2]) + (n * 256,)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=mag.device)
         elif tuple(self._cuda_f32(out, "out").shape) != shape or out.device != mag.device:
             raise ValueError("out must be %s on mag's device" % (shape,))
         stream = torch.cuda.current_stream(mag.device).cuda_stream
-        if hops is None:
+        if noisy is not None:
+            counts = None if hops is None else self._device_counts(hops, n, mag, "hops")
+            _check(self._lib, self._lib.nutls_istft_block_mix(self._h, mag.data_ptr(), noisy.data_ptr(), out.data_ptr(), n, counts, dc, stream))
+        elif hops is None:
             _check(self._lib, self._lib.nutls_istft_block(self._h, mag.data_ptr(), out.data_ptr(), n, dc, stream))
         else:
             _check(self._lib, self._lib.nutls_istft_block_ragged(self._h, mag.data_ptr(), out.data_ptr(), n, self._device_counts(hops, n, mag, "hops"), dc, stream))
@@ -1035,12 +1092,16 @@ class NutlsOffline(_PcmFormat):
         _check(self._lib, self._lib.nutls_enhance_block_host(self._h, _fptr(pcm), _fptr(out), pcm.shape[1] // 256, dc))
         return out
 
-    def enhance(self, wave, dc_mode: str = "edge") -> np.ndarray:
+    def enhance(self, wave, dc_mode: str = "edge", atten_lim_db=None) -> np.ndarray:
         """``wave [N]`` (one utterance) or ``[utterances, N]`` float, any N -> the enhanced waveform of the same shape, in the alignment
         of ``stream_enhance.enhance_batch_on_device`` / ``real_time_speech_enhancer`` (the first output hop, the leading half window,
         is dropped: interpreter_proposed.py:368).  ``(N - 256) // 256`` hops run in blocks of ``max_frames`` through
-        ``nutls_enhance_block_host``; previous hop, overlap tail and model state carry on into the next call until :meth:`reset`."""
+        ``nutls_enhance_block_host``; previous hop, overlap tail and model state carry on into the next call until :meth:`reset`.
+        ``atten_lim_db``: a cap in dB on the noise removed, a scalar or one value per utterance (``set_atten_limit(db=...)``, which stays in
+        force afterwards); ``None`` leaves the handle's limits as they are."""
         self._dc(dc_mode)
+        if atten_lim_db is not None:
+            self.set_atten_limit(db=atten_lim_db)
         x = np.asarray(wave, dtype=np.float32)
         batched = x.ndim == 2
         if x.ndim == 1 and self.utterances == 1:
@@ -1199,11 +1260,14 @@ class NutlsOffline(_PcmFormat):
                 o[a:a + len(g)] = g
         return outs
 
-    def enhance_ragged(self, waves_list, dc_mode: str = "edge") -> List[np.ndarray]:
+    def enhance_ragged(self, waves_list, dc_mode: str = "edge", atten_lim_db=None) -> List[np.ndarray]:
         """``utterances`` waveforms ``[N_u]`` of ANY lengths -> the enhanced waveforms, same lengths, each in the alignment of
         :meth:`enhance` (``(N_u - 256) // 256`` hops, the first output hop dropped); blocks of ``max_frames`` hops through
-        ``nutls_enhance_block_ragged_host``.  Previous hop, overlap tail and model state of every utterance carry on until :meth:`reset`."""
+        ``nutls_enhance_block_ragged_host``.  Previous hop, overlap tail and model state of every utterance carry on until :meth:`reset`.
+        ``atten_lim_db``: as in :meth:`enhance`."""
         dc = self._dc(dc_mode)
+        if atten_lim_db is not None:
+            self.set_atten_limit(db=atten_lim_db)
         waves = self._ragged_list(waves_list, "waves_list", 1)
         hops = [max(0, (len(w) - 256) // 256) for w in waves]
         outs = [np.zeros(len(w) + 256, np.float64) for w in waves]
@@ -1223,9 +1287,34 @@ class NutlsOffline(_PcmFormat):
         dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
         handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format, which turns the upper band
         (``set_pcm_upper_band``) and with it its following gain (``set_pcm_upper_follow``) off: the results are band-limited to 8 kHz."""
+        return self._enhance_many(waves, dc_mode, rate, None)
+
+    def enhance_many_atten(self, waves, atten_lim_db, dc_mode: str = "edge", rate: Optional[int] = None) -> List[np.ndarray]:
+        """:meth:`enhance_many` with an attenuation limit per recording: ``atten_lim_db`` a cap in dB on the noise removed, a scalar for
+        every recording or one value per recording, ``None`` entries for no cap (``set_atten_limit``).  The scheduler sets a slot's limit
+        when it hands the slot a recording; each result is what :meth:`enhance` of a fresh one-utterance handle returns for that recording
+        with its ``atten_lim_db``.  The limits of the last recordings stay in force on the slots afterwards.  (A method of its own:
+        ``enhance_many`` keeps the signature it has.)"""
+        n = len(waves)
+        seq = list(atten_lim_db) if isinstance(atten_lim_db, (list, tuple, np.ndarray)) else [atten_lim_db] * n
+        if len(seq) != n:
+            raise ValueError("atten_lim_db must be a scalar or one value per recording (%d), got %d" % (n, len(seq)))
+        return self._enhance_many(waves, dc_mode, rate, [atten_limit_from_db(d) for d in seq])
+
+    def _slot_limits(self, block, limits):
+        """The scheduler's hand-over of :meth:`enhance_many_atten`: the slots of ``block`` that take a new recording get its limit."""
+        new = [] if limits is None else [(slot, limits[item]) for slot, item, _, _, reset_before in block if reset_before]
+        if not new:
+            return
+        cur = self.atten_limit
+        for slot, l in new:
+            cur[slot] = l
+        self.set_atten_limit(limit=cur)
+
+    def _enhance_many(self, waves, dc_mode, rate, limits) -> List[np.ndarray]:
         dc = self._dc(dc_mode)
         if rate is not None:
-            return self._enhance_many_pcm(waves, dc, rate)
+            return self._enhance_many_pcm(waves, dc, rate, limits)
         waves = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
         if any(w.ndim != 1 for w in waves):
             raise ValueError("waves must be one-dimensional arrays")
@@ -1238,6 +1327,7 @@ class NutlsOffline(_PcmFormat):
                 if reset_before:
                     self.reset_utterance(slot)
                 chunks[slot] = waves[item][first * 256:(first + count) * 256]
+            self._slot_limits(block, limits)
             got = self._ragged_host(self._lib.nutls_enhance_block_ragged_host, chunks, 256, dc)
             for slot, item, first, count, _ in block:
                 outs[item][first * 256:(first + count) * 256] = got[slot]
@@ -1245,7 +1335,7 @@ class NutlsOffline(_PcmFormat):
 
     _PCM_RATES = (8000, 16000, 32000, 48000)
 
-    def _enhance_many_pcm(self, waves, dc: int, rate) -> List[np.ndarray]:
+    def _enhance_many_pcm(self, waves, dc: int, rate, limits=None) -> List[np.ndarray]:
         """:meth:`enhance_many` in the callers' format.  Every recording is padded with zeros to whole hops that cover ``N + lag`` samples,
         ``lag = pcm_hop_samples + pcm_delay_samples`` (the rule of :meth:`_wave_through_blocks`), and the lag is dropped from the front."""
         waves = [np.asarray(w) for w in waves]
@@ -1276,6 +1366,7 @@ class NutlsOffline(_PcmFormat):
                 if reset_before:
                     self.reset_utterance(slot)
                 chunks[slot] = padded[item][first * S:(first + count) * S]
+            self._slot_limits(block, limits)
             got = self._ragged_host(self._lib.nutls_enhance_block_pcm_ragged_host, chunks, S, dc, dtype=dtype)
             for slot, item, first, count, _ in block:
                 outs[item][first * S:(first + count) * S] = got[slot]

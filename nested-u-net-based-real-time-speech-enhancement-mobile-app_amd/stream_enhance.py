@@ -106,8 +106,21 @@ def overlap_add(blocks: np.ndarray, total: int) -> np.ndarray:
     return out
 
 
+def mix_magnitudes(noisy: np.ndarray, est: np.ndarray, limit) -> np.ndarray:
+    """The attenuation limit on the CPU (``nutls_set_atten_limit``): float32 ``m' = l * noisy + c * est`` with the float32 ``l`` (a scalar or
+    an array that broadcasts against the rows), ``c = float32(1.0 - float64(l))``, the sum taken in double and rounded once.  Products of two
+    float32 are exact in double, so ``l = 0`` returns ``est`` and ``l = 1`` returns ``noisy`` bit for bit, as the kernels do; in between the
+    kernels round ``c * est`` before their fma, one float32 rounding more than this."""
+    l32 = np.asarray(limit, np.float32)
+    if not np.all((l32 >= 0) & (l32 <= 1)):
+        raise ValueError("limit must lie in [0, 1]")
+    c32 = (1.0 - l32.astype(np.float64)).astype(np.float32)
+    x, e = np.asarray(noisy, np.float32).astype(np.float64), np.asarray(est, np.float32).astype(np.float64)
+    return (l32.astype(np.float64) * x + c32.astype(np.float64) * e).astype(np.float32)
+
+
 def real_time_speech_enhancer(noisy_speech: np.ndarray, runner: Callable[..., Dict[str, np.ndarray]],
-                              dc_mode: str = "edge", variant: str = None) -> Tuple[np.ndarray, List[float]]:
+                              dc_mode: str = "edge", variant: str = None, atten_limit: float = 0.0) -> Tuple[np.ndarray, List[float]]:
     """Frame-by-frame enhancement of one utterance; returns (waveform, seconds per frame).  The seconds cover what the
     reference's ``time_array`` covers (interpreter_proposed.py:201-366: the whole loop body -- buffer shift and rfft, model call,
     irfft, overlap-add): the frame's model call + synthesis as measured, plus its share of the analysis and of the overlap-add,
@@ -119,7 +132,10 @@ def real_time_speech_enhancer(noisy_speech: np.ndarray, runner: Callable[..., Di
     or ``"baseline"`` ('nutls', interpreter_nunet_tls.py:549); default: what the runner says (``signature_key``).
 
     ``dc_mode``: how bin 0 is re-created after the 256-bin model: ``"edge"`` (the PC loop,
-    interpreter_proposed.py:352-353: bin 0 = bin 1) or ``"zero"`` (the phone, mobile_app/.../RTSE_NUTLS_LSTM.java:677)."""
+    interpreter_proposed.py:352-353: bin 0 = bin 1) or ``"zero"`` (the phone, mobile_app/.../RTSE_NUTLS_LSTM.java:677).
+
+    ``atten_limit``: the attenuation limit ``l`` in [0, 1] (:func:`mix_magnitudes` of the frame's noisy magnitudes and the model's, in front
+    of the DC rule); 0.0, the default, is the reference's loop."""
     if dc_mode not in ("edge", "zero"):
         raise ValueError("dc_mode must be 'edge' or 'zero'")
     if variant is None:
@@ -139,6 +155,8 @@ def real_time_speech_enhancer(noisy_speech: np.ndarray, runner: Callable[..., Di
         outputs = runner(**feeds_from_outputs(outputs, model_in, variant))
         est = np.empty(FRAME_LEN // 2 + 1)
         est[1:] = outputs["model_out"].reshape(-1)
+        if atten_limit:
+            est[1:] = mix_magnitudes(model_in.reshape(-1), est[1:], atten_limit)
         est[0] = est[1] if dc_mode == "edge" else 0.0
         blocks[i] = np.fft.irfft(est * rotors[i]).astype(np.float32) * inv_win
         seconds.append(time.time() - t0)

@@ -13,8 +13,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("directory")
 ap.add_argument("--out", default=None)
 ap.add_argument("--dc-mode", default="edge", choices=["edge", "zero"])
+ap.add_argument("--atten-lim-db", type=float, default=None, help="cap in dB on the noise removed (default: none, the model's full suppression)")
 a = ap.parse_args()
-rows = evaluate_directory(a.directory, a.out, a.dc_mode)
+rows = evaluate_directory(a.directory, a.out, a.dc_mode, atten_lim_db=a.atten_lim_db)
 print("%-16s %7s %12s %12s %12s %12s" % ("clip", "sec", "SNR before", "SNR after", "SI-SNR bef.", "SI-SNR aft."))
 for r in rows:
     print("%-16s %7.2f %12.2f %12.2f %12.2f %12.2f" % (r["name"], r["seconds"], r["snr_before"], r["snr_after"], r["sisnr_before"], r["sisnr_after"]))
