@@ -20,6 +20,12 @@
  * Plain pointers and sizes only.  Every entry returns 0 on success or a negative code;
  * nutls_last_error() returns a thread-local message for the last failure.
  * One handle = one GPU = one host thread at a time (like a TF-Lite Interpreter).
+ * Stream order: calls on one handle take effect in the order they are made, whichever streams they name, the _host entries' private
+ * stream included.  A stream named in a call must outlive the handle's next call.  (nutls_step(h, ..., side) followed at once by
+ * nutls_step_host(h, ...), by a step on another stream or by one with stream = NULL needs no synchronisation in between: a call that names
+ * another stream than the call before it first waits, on the device, for an event recorded on that call's stream -- which is why that
+ * stream must still exist.  Calls that stay on one stream pay a pointer compare.  What the CALLER queues on its streams -- the copies that
+ * fill mag_in, the kernels that read mag_out -- is ordered by the caller, on the stream it hands over.)
  */
 #ifndef NUTLS_H_
 #define NUTLS_H_

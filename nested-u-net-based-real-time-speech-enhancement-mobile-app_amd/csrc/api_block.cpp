@@ -59,6 +59,7 @@ int upload_counts(Engine* e, const int* counts, int n, const char* who) {
       return fail(NUTLS_ERR_ARG, std::string(who) + ": count " + std::to_string(counts[u]) + " of utterance " + std::to_string(u) + " is outside 0 .. " + std::to_string(n));
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = dev_alloc_once(e, static_cast<size_t>(e->outt), &e->d_counts, false)) return rc;
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   HIP_TRY(hipMemcpyAsync(e->d_counts, counts, static_cast<size_t>(e->outt) * sizeof(int), hipMemcpyHostToDevice, e->stream));
   return NUTLS_OK;
 }
@@ -109,6 +110,7 @@ static int block_dc(int dc_mode, const char* who) {
 static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_hops, hipStream_t s, const int* hops = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
+  if (int rc = enqueue_on(e, s)) return rc;
   if (hops) HIP_TRY(launch_stft_block_ragged(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, hops, e->outt, n_hops, s));
   else HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, e->outt, n_hops, s));
   e->fb_tail_par ^= 1;
@@ -122,6 +124,7 @@ static int istft_block_launch(Engine* e, const float* mag, const float* noisy, f
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
   if (n_hops != e->fb_hops) return fail(NUTLS_ERR_ARG, "nutls_istft_block: n_hops differs from the block the phasors inside the handle belong to (nutls_stft_block first)");
+  if (int rc = enqueue_on(e, s)) return rc;
   if (noisy && e->atten_on)
     HIP_TRY(launch_istft_block_mix(mag, noisy, e->d_atten, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
                                    dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
@@ -248,6 +251,7 @@ static int process_block_impl(nutls_handle* h, const float* mag_in, float* mag_o
     return fail(NUTLS_ERR_ARG, std::string(who) + ": with frame counts the magnitude buffers must be 16-byte aligned");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = enqueue_on(e, s)) return rc;
   const int U = e->outt;
   const size_t bytes = static_cast<size_t>(U) * n_frames * NUTLS_BINS * sizeof(float);
   if (frames) {
@@ -421,12 +425,14 @@ static int block_host(nutls_handle* h, const float* in, float* out, int n, const
   const int* const d_counts = counts ? e->d_counts : nullptr;
   // (ragged: the rows behind the counts cross the link too and are zeroed on the device -- the stage-in kernel runs in place on the library's buffer)
   const size_t bytes = static_cast<size_t>(e->outt) * n * (wave ? NUTLS_FRAME_STEP : NUTLS_BINS) * sizeof(float);
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   HIP_TRY(hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, e->stream));
   if (int rc = wave ? nutls_enhance_block_ragged(h, d_in, d_out, n, d_counts, dc_mode, e->stream)
                     : process_block_impl(h, d_in, d_out, n, d_counts, false, e->stream, who))
     return rc;
   HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   return NUTLS_OK;
 }
 

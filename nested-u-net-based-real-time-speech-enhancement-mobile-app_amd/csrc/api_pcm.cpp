@@ -101,6 +101,7 @@ int zero_histories(Engine* e, int idx) {
 // With follow on top it is the kernel whose gain follows the model; follow's carried state is the encode half's and flips with enc_par.
 int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
+  if (int rc = enqueue_on(e, s)) return rc;
   const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
   if (st.upper != 0.f && st.follow) {
     const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
@@ -118,6 +119,7 @@ int decode_launch(Engine* e, const void* in, float* out, const unsigned char* ac
 
 int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
+  if (int rc = enqueue_on(e, s)) return rc;
   const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
   if (st.upper != 0.f && st.follow) {
     const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
@@ -189,6 +191,7 @@ int hop_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned 
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = pcm_init(e)) return rc;
   if (int rc = raw_init(e)) return rc;
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   const unsigned char* d_act = nullptr;
   if (active) {
     if (int rc = dev_alloc_once(e, static_cast<size_t>(e->B), &e->pcm.d_active, false)) return rc;
@@ -200,6 +203,7 @@ int hop_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned 
   if (int rc = hop_device(h, e->pcm.raw_in, e->pcm.raw_out, d_act, dc_mode, e->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   return NUTLS_OK;
 }
 
@@ -424,10 +428,12 @@ int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_
   if (int rc = pcm_init(e)) return rc;
   if (int rc = raw_init(e)) return rc;
   const size_t bytes = static_cast<size_t>(e->outt) * n_hops * hop_samples(e) * sample_bytes(e);
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
   if (int rc = block_device(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, dc_mode, e->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   return NUTLS_OK;
 }
 
@@ -479,6 +485,7 @@ int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, voi
   if (int rc = block_device_ragged(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, e->d_counts, dc_mode, e->stream)) return rc;
   HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   return NUTLS_OK;
 }
 

@@ -137,6 +137,7 @@ int nutls_profile_step(nutls_handle* h, float* ms, int n) {
   HIP_TRY(hipSetDevice(e->device));
   std::vector<hipEvent_t> ev(plan.size() + 1);
   for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
+  if (int rc = enqueue_on(e, e->stream)) return rc;
   if (int rc = begin_per_layer_step(e, e->stream)) return rc;
   HIP_TRY(hipEventRecord(ev[0], e->stream));
   for (size_t i = 0; i < plan.size(); ++i) {
@@ -218,6 +219,7 @@ int nutls_profile_production(nutls_handle* h, double* cum_us, int n, int reps, i
   if (n != nops + 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: n must equal nutls_fused_num_ops(variant) + 1");
   if (reps < 1 || steps < 1) return fail(NUTLS_ERR_ARG, "nutls_profile_production: reps and steps must be positive");
   HIP_TRY(hipSetDevice(e->device));
+  if (int rc = enqueue_on(e, e->stream)) return rc;
   HIP_TRY(fused_step_stop_set_attributes());
   hipEvent_t ev[2];
   HIP_TRY(hipEventCreate(&ev[0]));
@@ -259,6 +261,7 @@ int nutls_profile_fused(nutls_handle* h, double* us, int n) {
     return fail(NUTLS_ERR_ARG, "nutls_profile_fused: n must equal nutls_fused_plan_num_ops(variant, nutls_streams_per_workgroup(h))");
   if (int rc = refuse_in_hop_fusion(e, "nutls_profile_fused")) return rc;
   HIP_TRY(hipSetDevice(e->device));
+  if (int rc = enqueue_on(e, e->stream)) return rc;
   const int par = e->next_parity;
   int rc = run_fused(e, par, e->stream, true);
   if (rc) return rc;

@@ -106,6 +106,7 @@ static int step_impl(nutls_handle* h, const float* mag_in, float* mag_out, const
   if (e->offline) return fail(NUTLS_ERR_ARG, "nutls_step: offline handle, use nutls_process_block");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = enqueue_on(e, s)) return rc;
   const size_t bytes = static_cast<size_t>(e->B) * NUTLS_BINS * sizeof(float);
   const bool direct = e->mode == 3;      // the fused kernel takes the caller's buffers as they are
   if (!direct && mag_in != e->io_in) HIP_TRY(hipMemcpyAsync(e->io_in, mag_in, bytes, hipMemcpyDeviceToDevice, s));
@@ -140,6 +141,7 @@ int nutls_step_active(nutls_handle* h, const float* mag_in, float* mag_out, cons
 static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, const unsigned char* active) {
   Engine* e = &h->eng;
   HIP_TRY(hipSetDevice(e->device));
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   const size_t bytes = static_cast<size_t>(e->B) * NUTLS_BINS * sizeof(float);
   const unsigned char* d_act = nullptr;
   if (active) {
@@ -153,6 +155,7 @@ static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, 
     if (rc) return rc;
     if (active) note_active(e, active);
     HIP_TRY(hipStreamSynchronize(e->stream));
+    enqueue_idle(e);
     return NUTLS_OK;
   }
   HostStage hs(mag_in, mag_out, bytes);
@@ -162,6 +165,7 @@ static int step_host_impl(nutls_handle* h, const float* mag_in, float* mag_out, 
   if (active) note_active(e, active);
   HIP_TRY(hipMemcpyAsync(hs.out, e->io_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   hs.finish();
   return NUTLS_OK;
 }
@@ -184,6 +188,7 @@ static int stft_hop_impl(nutls_handle* h, const float* pcm_in, const unsigned ch
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
+  if ((rc = enqueue_on(e, static_cast<hipStream_t>(stream)))) return rc;
   HIP_TRY(launch_stft_hop(pcm_in, e->fe_tail, e->fe_win, e->fe_tw, e->io_in, e->fe_ph, e->B, static_cast<hipStream_t>(stream), active));
   return NUTLS_OK;
 }
@@ -200,6 +205,7 @@ static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const un
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
+  if ((rc = enqueue_on(e, static_cast<hipStream_t>(stream)))) return rc;
   // an attenuation limit in force (nutls_set_atten_limit): the mix kernel for the whole launch, the noisy rows being io_in as the analysis left them
   // (an offline handle's limits are per utterance, not per arena slot: they belong to its block entries)
   if (e->atten_on && !e->offline)
@@ -240,6 +246,7 @@ static int enhance_hop_fused(nutls_handle* h, const float* pcm_in, float* pcm_ou
   Engine* e = &h->eng;
   if (int rc = check_hop_fusion(e, "nutls_enhance_hop")) return rc;      // (cannot fail: everything that would is refused while fusion is on)
   HIP_TRY(hipSetDevice(e->device));
+  if (int rc = enqueue_on(e, static_cast<hipStream_t>(stream))) return rc;
   const FzHop hop{pcm_in, pcm_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dc_mode == NUTLS_DC_EDGE ? 1 : 0};
   const int par = e->next_parity;
   if (int rc = run_fused(e, par, static_cast<hipStream_t>(stream), false, e->io_in, e->io_out, active, &hop)) return rc;
@@ -282,6 +289,7 @@ static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pc
   HIP_TRY(hipSetDevice(e->device));
   int rc = frontend_init(e);
   if (rc) return rc;
+  if ((rc = enqueue_on(e, e->stream))) return rc;      // (behind what earlier calls queued on the callers' streams)
   const size_t bytes = static_cast<size_t>(e->B) * NUTLS_FRAME_STEP * sizeof(float);
   const unsigned char* d_act = nullptr;
   if (active) {
@@ -294,6 +302,7 @@ static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pc
     if ((rc = enhance_hop_impl(h, pcm_in, pcm_out, d_act, dc_mode, e->stream))) return rc;
     if (active) note_active(e, active);
     HIP_TRY(hipStreamSynchronize(e->stream));
+    enqueue_idle(e);
     return NUTLS_OK;
   }
   HostStage hs(pcm_in, pcm_out, bytes);
@@ -302,6 +311,7 @@ static int enhance_hop_host_impl(nutls_handle* h, const float* pcm_in, float* pc
   if (active) note_active(e, active);
   HIP_TRY(hipMemcpyAsync(hs.out, e->fe_pcm_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
   hs.finish();
   return NUTLS_OK;
 }

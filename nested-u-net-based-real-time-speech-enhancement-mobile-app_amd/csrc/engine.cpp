@@ -886,6 +886,18 @@ static int capture_graphs(Engine* e) {
   return NUTLS_OK;
 }
 
+// ---- stream order ---------------------------------------------------------------------------
+// The slow path of enqueue_on: this call names another stream than the last one.
+int order_after_last(Engine* e, hipStream_t s) {
+  if (e->last_stream != e->no_stream()) {
+    if (!e->ev_order) HIP_TRY(hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(e->ev_order, e->last_stream));
+    HIP_TRY(hipStreamWaitEvent(s, e->ev_order, 0));
+  }
+  e->last_stream = s;
+  return NUTLS_OK;
+}
+
 // ---- frame bookkeeping ----------------------------------------------------------------------
 // A frame of every stream has been enqueued: the next step writes the other parity.  The only place that flips the parity and counts frames.
 void advance_frame(Engine* e) {
@@ -899,6 +911,7 @@ int host_access_begin(Engine* e) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rcm = states_materialize(e, nullptr)) return rcm;      // (lazily written states: brought up to date before anything outside the kernel looks)
   HIP_TRY(hipDeviceSynchronize());
+  enqueue_idle(e);
   return NUTLS_OK;
 }
 

@@ -96,6 +96,12 @@ struct Engine {
                          // (2 was the plan-interpreter kernel of rounds 1-3, retired)
   int n_cu = 256;
   hipStream_t stream = nullptr;
+  // Stream order (nutls.h: calls on one handle take effect in the order they are made, whichever streams they name): the stream the last call
+  // enqueued on -- a caller's, the NULL stream or `stream` above; the Engine's own address while there is none, or after a call that left
+  // the device idle.  A call that names another stream waits for an event recorded on this one first: enqueue_on, below.
+  hipStream_t last_stream = no_stream();
+  hipEvent_t ev_order = nullptr;         // created by the first change of stream
+  hipStream_t no_stream() const { return reinterpret_cast<hipStream_t>(const_cast<Engine*>(this)); }
   std::vector<void*> allocs;
   float* arena = nullptr;        // stream-major arena: stream b's tensors at arena + b*sstride + slot offset
   size_t sstride = 0;            // floats per stream
@@ -204,6 +210,7 @@ struct Engine {
     for (void* p : allocs) (void)hipFree(p);
     for (hipEvent_t ev : oev) (void)hipEventDestroy(ev);
     if (oev_fork) (void)hipEventDestroy(oev_fork);
+    if (ev_order) (void)hipEventDestroy(ev_order);
     for (hipStream_t st : ostream) (void)hipStreamDestroy(st);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -223,6 +230,13 @@ int dev_alloc_once(Engine* e, size_t n, T** out, bool zero) {
   *out = static_cast<T*>(p);
   return NUTLS_OK;
 }
+
+// Before a call enqueues anything on stream s (the handle's device is current): on the stream of the call before it, a pointer compare and
+// nothing else; on another one, one event recorded on the old stream and awaited on s (order_after_last), so that the call's work runs
+// behind everything the handle has queued so far.  enqueue_idle: the call has synchronised with all of that -- there is nothing to wait for.
+int order_after_last(Engine* e, hipStream_t s);
+inline int enqueue_on(Engine* e, hipStream_t s) { return s == e->last_stream ? NUTLS_OK : order_after_last(e, s); }
+inline void enqueue_idle(Engine* e) { e->last_stream = e->no_stream(); }
 
 hipError_t run_launch(const Launch& L, hipStream_t s, const ConvKnobs& kn);
 int run_plan(Engine* e, int par, hipStream_t s);
