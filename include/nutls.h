@@ -100,7 +100,8 @@ int nutls_step_host(nutls_handle* h, const float* mag_in, float* mag_out);
  *   - its row of mag_in / pcm_in has no effect (it may hold anything, NaN included).  It is not even read where the stream's whole
  *     workgroup is held -- always on the one-stream plan; on a packed plan a workgroup with held AND active slots runs the step for all
  *     of them, so the row is read and computed on there, and the results are then replaced by the held state and the zero row;
- *   - its row of mag_out / pcm_out is written with ZEROS (deterministic: never stale data, never the input).
+ *   - its row of mag_out / pcm_out is written with ZEROS (deterministic: never stale data, never the input).  (The _pcm entries of a handle
+ *     in a G.711 format write the format's SILENCE code, 0xFF or 0xD5, in place of zero bytes: "PCM gateway", G.711.)
  * A stream that takes frames x0, x1, x2 at ticks 0, 3 and 4 produces the same bits -- outputs and states -- as one that took them at
  * ticks 0, 1 and 2; a held tick costs it nothing but time.  The other streams are not affected in any bit.  A new call joins a slot with
  * nutls_reset(h, b).  (The handle-wide state parity still flips on every call: a held stream's state is copied across, which is
@@ -287,7 +288,8 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * (AudioFormat.ENCODING_PCM_16BIT).  A handle is told its callers' format once; the _pcm entries below then take and return that audio and
  * keep the resampler state per stream, next to the state the library already owns.
  *
- * Format: rate_hz = 8000, 16000, 32000 or 48000; sample_format = NUTLS_PCM_F32 or NUTLS_PCM_S16.  A hop stays 16 ms at every rate:
+ * Format: rate_hz = 8000, 16000, 32000 or 48000; sample_format = NUTLS_PCM_F32 or NUTLS_PCM_S16 (at 8000 also NUTLS_PCM_ULAW or
+ * NUTLS_PCM_ALAW, one byte per sample: "G.711" below).  A hop stays 16 ms at every rate:
  * S = 256 * rate / 16000 samples (128, 256, 512, 768).  Buffers are [B, S] (hops) / [utterances, n_hops * S] (blocks) of the sample type,
  * rows contiguous, base pointer 16-byte aligned.  A handle starts at 16000 / NUTLS_PCM_F32.  nutls_set_pcm_format may be called between any
  * two hops; it zeroes every stream's resampler history (as a mode switch starts a new history) and synchronises the device.  Another rate or
@@ -297,6 +299,38 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  *
  * Samples: int16 -> float is s / 32768 (exact); float -> int16 is y * 32768 rounded to nearest even and clamped to -32768 .. 32767, NaN -> 0.
  * The float that is quantised is bit for bit the value the NUTLS_PCM_F32 format returns.
+ *
+ * G.711 (NUTLS_PCM_ULAW, NUTLS_PCM_ALAW; 8000 Hz ONLY): what telephony delivers on the wire -- RTP payload types 0 (PCMU) and 8 (PCMA), the
+ * .wav / .au archives of call recordings -- is one BYTE per sample, mu-law or A-law.  Buffers are [B, 128] bytes for a hop and
+ * [utterances, n_hops * 128] bytes for a block, rows contiguous, base pointer 16-byte aligned; nutls_pcm_hop_samples and
+ * nutls_pcm_delay_samples are what they are at 8 kHz (128 and 48).  Either format at any other rate is NUTLS_ERR_ARG and changes nothing: an
+ * explicit request never silently becomes another format.  Everything else about a format switch is as above.  The companding is a pure
+ * bit rule, exact in both directions (the rules of the widely used g711.c and of CPython's audioop.ulaw2lin / alaw2lin / lin2ulaw / lin2alaw
+ * at width 2), with c the byte and >> an arithmetic shift:
+ *   expansion (decode): the code is mapped to an int16 value s, then s / 32768 exactly; from there on the chain is the int16 format's, so a
+ *   companded handle fed codes c and an int16 handle fed expand(c) produce the same bits everywhere downstream.
+ *     mu-law: u = ~c & 0xFF; t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4); s = (u & 0x80) ? 0x84 - t : t - 0x84.       Range +-32124.
+ *     A-law:  a = c ^ 0x55; t = (a & 15) << 4; g = (a & 0x70) >> 4; t = g == 0 ? t + 8 : (t + 0x108) << (g - 1); s = (a & 0x80) ? t : -t.
+ *             Range +-32256.
+ *   compression (encode): the float is first quantised to int16 s exactly as NUTLS_PCM_S16 does it (y * 32768, round to nearest even, clamp,
+ *   NaN -> 0: bit for bit the value the int16 format returns), then
+ *     mu-law: v = s >> 2; if v < 0: v = -v, mask = 0x7F, else mask = 0xFF; v = min(v, 8159) + 33; seg = how many of the ends 0x3F, 0x7F, 0xFF,
+ *             0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF v exceeds; code = (seg >= 8 ? 0x7F : (seg << 4) | ((v >> (seg + 1)) & 15)) ^ mask.
+ *     A-law:  v = s >> 3; if v < 0: v = -v - 1, mask = 0x55, else mask = 0xD5; seg counted over 0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF,
+ *             0xFFF; code = (seg >= 8 ? 0x7F : (seg << 4) | ((seg < 2 ? v >> 1 : v >> seg) & 15)) ^ mask.
+ *   - mu-law never produces 0x7F: that code is negative zero, 0xFF is produced instead.  Every A-law code is a fixed point of expand ->
+ *     compress, and so is every mu-law code except 0x7F.
+ *   - SILENCE, NOT ZEROS: a zero byte is full-scale negative in mu-law and -5504 in A-law.  Wherever this header says that a row or hop of
+ *     pcm_out is written with ZEROS -- a held stream under an `active` mask, the hops behind a ragged count -- a companded handle writes the
+ *     format's silence code instead: 0xFF (mu-law) or 0xD5 (A-law), what compressing a zero hop gives; it expands to 0 and to +8.
+ *   - nutls_pcm_g711_expand(fmt, table, 256) and nutls_pcm_g711_compress(fmt, in, out, n) are the library's statement of the rule, host only,
+ *     no handle and no GPU, as nutls_pcm_filter is: the int16 value of each of the 256 codes, and the codes of n int16 values.  A format other
+ *     than the two, a null pointer or a table length other than 256 is NUTLS_ERR_ARG, and nothing is written.  The kernels agree with them bit
+ *     for bit.
+ *   - Every _pcm entry at 8 kHz honours the two formats: the hop entries (nutls_enhance_hop_pcm, _active, _host, _host_active), the halves
+ *     nutls_pcm_decode_hop / nutls_pcm_encode_hop, the block entries (nutls_enhance_block_pcm, _host, the _ragged forms) and the block halves
+ *     with and without counts; hop fusion on or off, the attenuation limit, masks, nutls_reset and in-place pcm_in == pcm_out apply
+ *     unchanged.  The upper band and follow are refused as on every 8 kHz handle.  The _host entries move a quarter of the float32 bytes.
  *
  * Rates: q = max(rate, 16000) / min(rate, 16000) = 2 or 3.  One linear-phase FIR prototype p[0 .. 2 K q] per rate, K = 24: a Kaiser-windowed
  * sinc (beta 8) with its cutoff at the LOWER rate's Nyquist frequency, designed in double when needed, normalised to sum 1 and rounded to
@@ -379,7 +413,7 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  *
  * State: per stream (utterance) and direction the library keeps the filter's last 2 K q input samples, outside the signature's tensors.
  * nutls_reset(h, b) zeroes stream b's (-1: everybody's).  A held stream (active[b] == 0) keeps it as it is -- neither kernel touches it -- and
- * its row of pcm_out is zeros; its row of pcm_in is not read.  An offline handle carries it from block to block.  Every output sample is the
+ * its row of pcm_out is zeros (G.711: the silence code, 0xFF / 0xD5, not zero bytes); its row of pcm_in is not read.  An offline handle carries it from block to block.  Every output sample is the
  * same sum, in the same order (taps ascending, one fp32 FMA each; the zero-stuffed terms skipped), over the same values wherever the hop or
  * block boundary falls: the two halves are bit-exact across every cut of a stream, between ticks 0, 3, 4 and ticks 0, 1, 2, and between the
  * hop entries of a streaming handle and the block entries of an offline one.
@@ -389,12 +423,18 @@ int nutls_istft_block_ragged(nutls_handle* h, const float* mag, float* pcm_out, 
  * _pcm entry decodes into a library buffer, calls that plain entry on library buffers and encodes: two small launches more per hop or block.
  * An offline handle gets NUTLS_ERR_ARG from the hop entries, a streaming handle from the block entries.
  * The _host entries copy the raw samples (pageable or nutls_host_alloc) into library buffers, run the pipeline and copy back; they
- * synchronise like their float twins -- int16 moves half the bytes over the link.  nutls_enhance_hop_pcm_host_active hands its mask on as
+ * synchronise like their float twins -- int16 moves half the bytes over the link, G.711 a quarter.  nutls_enhance_hop_pcm_host_active hands its mask on as
  * a device mask (see nutls_step_active on nutls_state_set and masks the host has not seen).  Ragged blocks in the callers' format: the
  * _pcm_ragged entries at the end of this section.  Zero-copy reads of pinned PCM stay out of scope: the _host entries copy. */
 #define NUTLS_PCM_F32 0   /* float32, unit scale (what nutls_enhance_hop takes) */
 #define NUTLS_PCM_S16 1   /* int16, little endian; 32768 = 1.0 */
+#define NUTLS_PCM_ULAW 2  /* G.711 mu-law, one byte per sample (RTP PCMU); 8000 Hz only */
+#define NUTLS_PCM_ALAW 3  /* G.711 A-law, one byte per sample (RTP PCMA); 8000 Hz only */
 int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format);   /* also turns the upper band off (gain 0), and follow with it */
+/* G.711 above, host only, no handle: table[256] = the int16 value of every code; out[n] = the codes of in[n].  sample_format: NUTLS_PCM_ULAW
+ * or NUTLS_PCM_ALAW.  Another format, a null pointer or n != 256 (expand) is NUTLS_ERR_ARG, and nothing is written. */
+int nutls_pcm_g711_expand(int sample_format, short* table, int n);
+int nutls_pcm_g711_compress(int sample_format, const short* in, unsigned char* out, size_t n);
 /* "Upper band" above.  gain in 0 .. 1, 0 = off (the default); NaN, a gain outside 0 .. 1, or a gain other than 0 at 8000 / 16000 Hz:
  * NUTLS_ERR_ARG, nothing changes.  Synchronises and zeroes every stream's resampler histories and upper-band state, unless the gain is the
  * one the handle already has.  nutls_set_pcm_format resets it to 0: call this after it. */
@@ -415,7 +455,8 @@ int nutls_enhance_hop_pcm_active(nutls_handle* h, const void* pcm_in, void* pcm_
 int nutls_enhance_hop_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode);
 int nutls_enhance_hop_pcm_host_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode);
 /* The two halves on their own (testing, custom models), as nutls_stft_hop / nutls_istft_hop are: the callers' format <-> DEVICE [B, 256]
- * float32 at 16 kHz.  `active`: DEVICE mask or NULL; a held row of the output is zeros.  Any streaming handle. */
+ * float32 at 16 kHz.  `active`: DEVICE mask or NULL; a held row of the output is zeros (of nutls_pcm_encode_hop in a G.711 format: the
+ * silence code, 0xFF / 0xD5).  Any streaming handle. */
 int nutls_pcm_decode_hop(nutls_handle* h, const void* pcm_in, float* hop_out, const unsigned char* active, void* stream);
 int nutls_pcm_encode_hop(nutls_handle* h, const float* hop_in, void* pcm_out, const unsigned char* active, void* stream);
 /* Offline handles (nutls_create_offline, nutls_create_offline_batch): DEVICE [utterances, n_hops * S] (HOST in the _host entry),
@@ -429,8 +470,8 @@ int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out,
  * nutls_enhance_block_pcm_ragged decodes with the counts, calls nutls_enhance_block_ragged on the library's float buffers and encodes with
  * the counts.  For utterance u, one call
  *   - writes hops 0 .. k-1 of pcm_out with exactly the bits nutls_enhance_block_pcm of the same width writes there;
- *   - writes hops k .. n_hops-1 of pcm_out with ZEROS; the matching hops of pcm_in are not read and may hold anything (NaN, any int16).  The
- *     caller's input buffer is never written;
+ *   - writes hops k .. n_hops-1 of pcm_out with ZEROS (a G.711 format: with the silence code, 0xFF / 0xD5, not zero bytes); the matching hops
+ *     of pcm_in are not read and may hold anything (NaN, any int16, any byte).  The caller's input buffer is never written;
  *   - carries the resampler history of both directions from hop k-1, and what nutls_enhance_block_ragged carries from frame k;
  *   - k = 0 HOLDS the utterance completely: both resampler histories, the previous hop, the overlap tail and the model state stay as they were.
  * Any cut of a recording into ragged calls gives the same concatenated samples, bit for bit.  hops == NULL: the call IS the entry without
@@ -439,7 +480,8 @@ int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out,
  * valid and unmodified until the work queued on `stream` has run.  The _host entry takes pcm_in, pcm_out and hops in HOST memory; a count
  * outside 0 .. n_hops, a bad dc_mode or n_hops, a null pointer or a streaming handle is NUTLS_ERR_ARG (nutls_last_error says which), checked
  * before anything is converted: a refused call leaves every history where it was.  The two halves: nutls_pcm_decode_block /
- * nutls_pcm_encode_block with counts; the 16 kHz side is [utterances, n_hops * 256] float32, its hops behind a count are zeros.
+ * nutls_pcm_encode_block with counts; the 16 kHz side is [utterances, n_hops * 256] float32, its hops behind a count are zeros (the callers'
+ * side of the encode half in a G.711 format: the silence code).
  * Cost: the uniform entry's (the kernels return early behind a count; the model computes and discards, see "Ragged blocks"). */
 int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
 int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode);

@@ -7,6 +7,8 @@
 // Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): with a gain other than 0 decode_launch / encode_launch start the kernels that also
 // form and add the band above 8 kHz -- every entry below goes through those two, so every entry honours the gain; with 0 nothing here differs.
 // Follow (nutls_set_pcm_upper_follow): the same two launches start the kernels whose gain follows the model; off, nothing here differs.
+// G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8000 Hz only): a format like the others -- nutls_set_pcm_format validates it, sample_bytes is 1, the
+// two plain launchers get the format code; nothing else here knows.  The rule itself is stated once on the host (g711_expand / g711_compress below).
 // The kernels: pcm.hip.
 #include <cstdint>
 
@@ -18,8 +20,51 @@ namespace {
 
 bool plain_format(const Engine* e) { return e->pcm.rate == 16000 && e->pcm.fmt == NUTLS_PCM_F32; }
 int hop_samples(const Engine* e) { return NUTLS_FRAME_STEP / 16 * (e->pcm.rate / 1000); }      // 256 * rate / 16000
-size_t sample_bytes(const Engine* e) { return e->pcm.fmt == NUTLS_PCM_S16 ? sizeof(short) : sizeof(float); }
+bool g711_format(int fmt) { return fmt == NUTLS_PCM_ULAW || fmt == NUTLS_PCM_ALAW; }
+size_t sample_bytes(const Engine* e) { return g711_format(e->pcm.fmt) ? 1 : e->pcm.fmt == NUTLS_PCM_S16 ? sizeof(short) : sizeof(float); }
 int max_hops(const Engine* e) { return e->offline ? e->offline : 1; }
+static_assert(NUTLS_PCM_F32 == kPcmFmtF32 && NUTLS_PCM_S16 == kPcmFmtS16 && NUTLS_PCM_ULAW == kPcmFmtUlaw && NUTLS_PCM_ALAW == kPcmFmtAlaw,
+              "the launchers of pcm.hpp take the format codes of nutls.h");
+
+// ---- G.711, the rule as nutls.h words it ("G.711"): what nutls_pcm_g711_expand / _compress return and what the kernels of pcm.hip agree with ----
+int g711_expand(int fmt, int c) {
+  if (fmt == NUTLS_PCM_ULAW) {
+    const int u = ~c & 0xFF;
+    const int t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4);
+    return (u & 0x80) ? 0x84 - t : t - 0x84;
+  }
+  const int a = c ^ 0x55;
+  int t = (a & 15) << 4;
+  const int g = (a & 0x70) >> 4;
+  t = g == 0 ? t + 8 : (t + 0x108) << (g - 1);
+  return (a & 0x80) ? t : -t;
+}
+
+int g711_segment(int v, int first_end) {      // how many of the 8 segment ends first_end, 2 first_end + 1, ... v exceeds
+  int seg = 0;
+  for (int end = first_end; seg < 8 && v > end; end = 2 * end + 1) ++seg;
+  return seg;
+}
+
+unsigned char g711_compress(int fmt, int s) {
+  if (fmt == NUTLS_PCM_ULAW) {
+    int v = s >> 2, mask = 0xFF;
+    if (v < 0) {
+      v = -v;
+      mask = 0x7F;
+    }
+    v = (v < 8159 ? v : 8159) + 33;
+    const int seg = g711_segment(v, 0x3F);
+    return static_cast<unsigned char>((seg >= 8 ? 0x7F : (seg << 4) | ((v >> (seg + 1)) & 15)) ^ mask);
+  }
+  int v = s >> 3, mask = 0xD5;
+  if (v < 0) {
+    v = -v - 1;
+    mask = 0x55;
+  }
+  const int seg = g711_segment(v, 0x1F);
+  return static_cast<unsigned char>((seg >= 8 ? 0x7F : (seg << 4) | ((seg < 2 ? v >> 1 : v >> seg) & 15)) ^ mask);
+}
 
 int upload_taps(Engine* e) {
   const std::vector<float> p = pcm_design(e->pcm.rate);
@@ -111,7 +156,7 @@ int decode_launch(Engine* e, const void* in, float* out, const unsigned char* ac
     const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
     HIP_TRY(launch_pcm_decode_upper(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
   } else {
-    HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+    HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt, st.rows, n_hops, s));
   }
   st.dec_par = nxt;
   return NUTLS_OK;
@@ -129,7 +174,7 @@ int encode_launch(Engine* e, const float* in, void* out, const unsigned char* ac
     const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
     HIP_TRY(launch_pcm_encode_upper(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
   } else {
-    HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, s));
+    HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt, st.rows, n_hops, s));
   }
   st.enc_par = nxt;
   return NUTLS_OK;
@@ -262,11 +307,30 @@ int nutls_pcm_filter(int rate_hz, float* taps, int n) {
   return NUTLS_OK;
 }
 
+// G.711, host only: the library's statement of the rule (no handle, no device)
+int nutls_pcm_g711_expand(int sample_format, short* table, int n) {
+  if (!g711_format(sample_format)) return fail(NUTLS_ERR_ARG, "nutls_pcm_g711_expand: sample format must be NUTLS_PCM_ULAW or NUTLS_PCM_ALAW");
+  if (!table) return fail(NUTLS_ERR_ARG, "nutls_pcm_g711_expand: null pointer");
+  if (n != 256) return fail(NUTLS_ERR_ARG, "nutls_pcm_g711_expand: the table has 256 entries, one per code: n must be 256");
+  for (int c = 0; c < 256; ++c) table[c] = static_cast<short>(g711_expand(sample_format, c));
+  return NUTLS_OK;
+}
+
+int nutls_pcm_g711_compress(int sample_format, const short* in, unsigned char* out, size_t n) {
+  if (!g711_format(sample_format)) return fail(NUTLS_ERR_ARG, "nutls_pcm_g711_compress: sample format must be NUTLS_PCM_ULAW or NUTLS_PCM_ALAW");
+  if (!in || !out) return fail(NUTLS_ERR_ARG, "nutls_pcm_g711_compress: null pointer");
+  for (size_t i = 0; i < n; ++i) out[i] = g711_compress(sample_format, in[i]);
+  return NUTLS_OK;
+}
+
 int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
   if (!h) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: null handle");
   if (!pcm_ratio(rate_hz)) return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: rate must be 8000, 16000, 32000 or 48000");
-  if (sample_format != NUTLS_PCM_F32 && sample_format != NUTLS_PCM_S16)
-    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: sample format must be NUTLS_PCM_F32 or NUTLS_PCM_S16");
+  if (sample_format != NUTLS_PCM_F32 && sample_format != NUTLS_PCM_S16 && !g711_format(sample_format))
+    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: sample format must be NUTLS_PCM_F32, NUTLS_PCM_S16, NUTLS_PCM_ULAW or NUTLS_PCM_ALAW");
+  if (g711_format(sample_format) && rate_hz != 8000)      // (an explicit request never silently becomes another format)
+    return fail(NUTLS_ERR_ARG, "nutls_set_pcm_format: NUTLS_PCM_ULAW and NUTLS_PCM_ALAW are G.711, which is 8 kHz: rate must be 8000 with them, not " +
+                                   std::to_string(rate_hz));
   Engine* e = &h->eng;
   const bool to_plain = rate_hz == 16000 && sample_format == NUTLS_PCM_F32;
   if (!e->pcm.ready && to_plain) {      // nothing has been converted yet and nothing will be

@@ -27,6 +27,14 @@
 // decoded samples of context computed again by every hop of a block but its first (+19 % of the decode chains); the encode adds one FMA.
 // Follow (nutls_set_pcm_upper_follow): the gain of out[n] follows the model, gamma_t[n] of nutls.h -- two more kernels again (pcm_hop<..., UPPER,
 // FOLLOW>), in the same two launches; one energy code for both halves (pcm_e2), every g a function of 5 a and 5 b, so one workgroup per (row, hop).
+// G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8 kHz only): two more sample types beside float32 and int16, one byte per sample (ulaw_t, alaw_t), so
+// four more kernels of the same body -- the 8 kHz decode and encode of each law; no other rate has them, and the kernels above are what the
+// other formats run.  A lane loads or stores 16 codes in its 16 bytes.  On the way in a code is expanded to its int16 value and that times
+// 2^-15 (exact): from there on the chain is the int16 format's.  On the way out the float is quantised by to_s16, the int16 format's rule,
+// and that value is compressed.  Both directions are integer bit operations (g711_expand, g711_compress: the segment of a sample from the
+// position of its leading bit, no table), exact, and agree with the host's statement of the rule (nutls_pcm_g711_expand / _compress, api_pcm.cpp)
+// for all 256 codes and all 65 536 int16 values.  Where the other formats write a zero hop (a held row, a hop behind a count), these write the
+// format's silence code -- 0xFF / 0xD5, what a zero hop compresses to: a zero BYTE is full-scale negative in mu-law and -5504 in A-law.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,6 +47,11 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// One byte of G.711, mu-law or A-law: two distinct types, so that stage_in / stage_out / zero_out resolve by overload like float and short
+struct ulaw_t { unsigned char code; };
+struct alaw_t { unsigned char code; };
 
 constexpr int kThreads = 256;
 
@@ -126,6 +139,88 @@ __device__ __forceinline__ void zero_out(short* dst, int count, int tid) {
   for (int i = tid; i < count / 8; i += kThreads) reinterpret_cast<s16x8*>(dst)[i] = z;
 }
 
+// ---- G.711: code <-> int16, integer bit operations (nutls.h, "G.711"; the host's statement of the same rule: api_pcm.cpp) ----------------------
+// expand: the int16 value of code c (0 .. 255) -- mu-law +-32124, A-law +-32256
+__device__ __forceinline__ int g711_expand(ulaw_t, unsigned c) {
+  const unsigned u = ~c & 0xFFu;
+  const int t = static_cast<int>((((u & 15u) << 3) + 0x84u) << ((u & 0x70u) >> 4));
+  return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ int g711_expand(alaw_t, unsigned c) {
+  const unsigned a = c ^ 0x55u;
+  const unsigned g = (a & 0x70u) >> 4;
+  int t = static_cast<int>((a & 15u) << 4);
+  t = g == 0 ? t + 8 : (t + 0x108) << (g - 1);
+  return (a & 0x80u) ? t : -t;
+}
+// compress: the code of the int16 value s.  The segment is the number of segment ends below the magnitude v: with the ends 2^(i + b) - 1,
+// i = 0 .. 7 (b = 6 for mu-law, whose v carries the bias 33 and so has its leading bit at 5 or above; b = 5 for A-law), that is the position
+// of v's leading bit minus (b - 1), and 0 for a v below the first end (A-law: v = 0 included, __clz(0) = 32).
+__device__ __forceinline__ unsigned g711_compress(ulaw_t, int s) {
+  int v = s >> 2;
+  unsigned mask = 0xFFu;
+  if (v < 0) {
+    v = -v;
+    mask = 0x7Fu;
+  }
+  v = min(v, 8159) + 33;                      // 33 .. 8192
+  const int seg = 26 - __clz(v);              // 0 .. 8 (8: v = 8192 alone)
+  const unsigned code = seg >= 8 ? 0x7Fu : static_cast<unsigned>((seg << 4) | ((v >> (seg + 1)) & 15));
+  return code ^ mask;
+}
+__device__ __forceinline__ unsigned g711_compress(alaw_t, int s) {
+  int v = s >> 3;
+  unsigned mask = 0xD5u;
+  if (v < 0) {
+    v = -v - 1;
+    mask = 0x55u;
+  }
+  const int seg = max(27 - __clz(v), 0);      // 0 .. 7 (v <= 4095)
+  const unsigned code = seg >= 8 ? 0x7Fu : static_cast<unsigned>((seg << 4) | ((seg < 2 ? v >> 1 : v >> seg) & 15));
+  return code ^ mask;
+}
+// what a zero hop compresses to, in every byte of a word
+__device__ __forceinline__ unsigned g711_silence4(ulaw_t) { return 0xFFFFFFFFu; }
+__device__ __forceinline__ unsigned g711_silence4(alaw_t) { return 0xD5D5D5D5u; }
+
+// 16 codes per lane and access (src / dst 16-byte aligned, count a multiple of 16); byte k of word w of a lane's 16 bytes is its sample 4 w + k
+template <typename G>
+__device__ __forceinline__ void g711_stage_in(const G* src, float* lds, int count, int tid) {
+  for (int i = tid; i < count / 16; i += kThreads) {
+    const u32x4 v = reinterpret_cast<const u32x4*>(src)[i];
+    for (int w = 0; w < 4; ++w) {
+      f32x4 f;
+      for (int k = 0; k < 4; ++k) f[k] = static_cast<float>(g711_expand(G{}, (v[w] >> (8 * k)) & 0xFFu)) * (1.f / 32768.f);      // exact
+      reinterpret_cast<f32x4*>(lds)[4 * i + w] = f;
+    }
+  }
+}
+template <typename G>
+__device__ __forceinline__ void g711_stage_out(const float* lds, G* dst, int count, int tid) {
+  for (int i = tid; i < count / 16; i += kThreads) {
+    u32x4 v;
+    for (int w = 0; w < 4; ++w) {
+      const f32x4 f = reinterpret_cast<const f32x4*>(lds)[4 * i + w];
+      unsigned word = 0;
+      for (int k = 0; k < 4; ++k) word |= g711_compress(G{}, to_s16(f[k])) << (8 * k);
+      v[w] = word;
+    }
+    reinterpret_cast<u32x4*>(dst)[i] = v;
+  }
+}
+template <typename G>
+__device__ __forceinline__ void g711_silence_out(G* dst, int count, int tid) {
+  const unsigned z = g711_silence4(G{});
+  const u32x4 v = {z, z, z, z};
+  for (int i = tid; i < count / 16; i += kThreads) reinterpret_cast<u32x4*>(dst)[i] = v;
+}
+__device__ __forceinline__ void stage_in(const ulaw_t* src, float* lds, int count, int tid) { g711_stage_in(src, lds, count, tid); }
+__device__ __forceinline__ void stage_in(const alaw_t* src, float* lds, int count, int tid) { g711_stage_in(src, lds, count, tid); }
+__device__ __forceinline__ void stage_out(const float* lds, ulaw_t* dst, int count, int tid) { g711_stage_out(lds, dst, count, tid); }
+__device__ __forceinline__ void stage_out(const float* lds, alaw_t* dst, int count, int tid) { g711_stage_out(lds, dst, count, tid); }
+__device__ __forceinline__ void zero_out(ulaw_t* dst, int count, int tid) { g711_silence_out(dst, count, tid); }      // "zero": the format's silence
+__device__ __forceinline__ void zero_out(alaw_t* dst, int count, int tid) { g711_silence_out(dst, count, tid); }
+
 // ---- follow: the upper band's gain follows the model (nutls.h, "Upper band", follow) ------------------------------------------------------------
 // Everything here is fp32 in one fixed order, each operation rounded on its own: the pragma keeps the compiler from contracting a product
 // into a sum, and / and __builtin_sqrtf are the correctly rounded ones (this file is built without fast-math).
@@ -195,6 +290,8 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
   constexpr int CARRY = DEC_UPPER ? kPcmUpCtx : kPcmMaxHop, NCARRY = DEC_UPPER ? YPRE : NOUT;      // a row's carried upper-band state: stride, floats in use
   static_assert(HIST <= kPcmMaxHist && HIST <= NIN && NIN <= kPcmMaxHop && NOUT <= kPcmMaxHop, "staging sizes");
   static_assert(HIST % 8 == 0 && NIN % 8 == 0 && NOUT % 8 == 0, "16-byte accesses");
+  // one-byte samples: 16 per access on the callers' side (the history is kept as floats: only a block's later hops stage HIST + XPRE codes from the row)
+  static_assert((sizeof(TI) != 1 || ((HIST + XPRE) % 16 == 0 && NIN % 16 == 0)) && (sizeof(TO) != 1 || NOUT % 16 == 0), "16-byte accesses, one-byte samples");
   static_assert(!FOLLOW || (UPPER && (UP ? NIN : NOUT) == kThreads && kThreads == 256), "follow: one lane per 16 kHz sample of the hop");
   static_assert(!UPPER || (Q > 1 && YPRE == (DEC_UPPER ? kPcmUpCtx : 0) && YPRE + NOUT <= kPcmMaxHop && XPRE + HIST <= NIN && XPRE % 8 == 0 && YPRE % 8 == 0), "upper band: staging sizes");
   __shared__ __attribute__((aligned(16))) float s_x[(DEC_UPPER ? kPcmMaxHist : 0) + kPcmMaxHist + kPcmMaxHop];
@@ -410,10 +507,16 @@ std::vector<float> pcm_design(int rate_hz) {
 }
 
 hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s) {
+  if (fmt == kPcmFmtUlaw || fmt == kPcmFmtAlaw) {      // G.711: 8 kHz alone has the kernels
+    if (rate_hz != 8000) return hipErrorInvalidValue;
+    return fmt == kPcmFmtUlaw ? decode_as<2, true, ulaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
+                              : decode_as<2, true, alaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s);
+  }
+  if (fmt != kPcmFmtF32 && fmt != kPcmFmtS16) return hipErrorInvalidValue;
 #define NUTLS_PCM_DECODE(Q, UP) \
-  return s16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
-             : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
+  return fmt == kPcmFmtS16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
+                           : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
   switch (rate_hz) {
     case 8000: NUTLS_PCM_DECODE(2, true);
     case 16000: NUTLS_PCM_DECODE(1, false);
@@ -425,10 +528,16 @@ hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, cons
 }
 
 hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s) {
+                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s) {
+  if (fmt == kPcmFmtUlaw || fmt == kPcmFmtAlaw) {
+    if (rate_hz != 8000) return hipErrorInvalidValue;
+    return fmt == kPcmFmtUlaw ? encode_as<2, false, ulaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
+                              : encode_as<2, false, alaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s);
+  }
+  if (fmt != kPcmFmtF32 && fmt != kPcmFmtS16) return hipErrorInvalidValue;
 #define NUTLS_PCM_ENCODE(Q, UP) \
-  return s16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
-             : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
+  return fmt == kPcmFmtS16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
+                           : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
   switch (rate_hz) {
     case 8000: NUTLS_PCM_ENCODE(2, false);
     case 16000: NUTLS_PCM_ENCODE(1, false);

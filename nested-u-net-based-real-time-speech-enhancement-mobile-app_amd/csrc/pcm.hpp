@@ -2,7 +2,7 @@
 // kernels (pcm.hip).  Kept apart from nutls_internal.hpp, like ragged.hpp: the frame-step kernels have nothing to do with these.
 //
 // The library side of both kernels is [rows, n_hops * 256] float32 at 16 kHz; the caller side is [rows, n_hops * S] samples of the handle's
-// format (float32 or int16) at its rate, S = 256 * rate / 16000.  q = max(rate, 16000) / min(rate, 16000) in {1, 2, 3}; the prototype
+// format (float32 or int16; at 8 kHz also one byte of G.711, mu-law or A-law) at its rate, S = 256 * rate / 16000.  q = max(rate, 16000) / min(rate, 16000) in {1, 2, 3}; the prototype
 // p[0 .. 2 K q] (K = kPcmK low-rate samples of delay per direction; one tap, 1.0, at 16 kHz) is pcm_design()'s.
 #pragma once
 
@@ -20,6 +20,8 @@ constexpr int kPcmUpCtx = 2 * kPcmK;                   // upper band: decoded sa
 constexpr int kPcmFollowHops = 4;                      // follow: hops of the two energy windows (NUTLS_PCM_FOLLOW_HOPS)
 constexpr int kPcmFollowCarry = 16;                    // follow: floats a row carries -- [0 .. 4] the last 5 a, [5 .. 8] the last 4 b (newest first), [9] the last g
 constexpr int kPcmFollowGainAt = 2 * kPcmFollowHops + 1;      // where g sits in them
+// The sample formats, as the launchers below take them in `fmt` (the values of NUTLS_PCM_F32, _S16, _ULAW and _ALAW: api_pcm.cpp asserts it)
+constexpr int kPcmFmtF32 = 0, kPcmFmtS16 = 1, kPcmFmtUlaw = 2, kPcmFmtAlaw = 3;
 
 // q of a supported rate (8000, 16000, 32000, 48000), else 0
 int pcm_ratio(int rate_hz);
@@ -30,7 +32,7 @@ std::vector<float> pcm_design(int rate_hz);
 // What a handle keeps for its callers' format: allocated when a _pcm entry first needs it (api_pcm.cpp), zeroed by nutls_set_pcm_format and,
 // row by row, by nutls_reset.
 struct PcmState {
-  int rate = 16000, fmt = 0;           // NUTLS_PCM_F32
+  int rate = 16000, fmt = 0;           // NUTLS_PCM_F32; 2 / 3 (G.711 mu-law / A-law, one byte per sample) at 8000 only
   bool ready = false;                  // the buffers below exist
   int rows = 0;                        // streams of a streaming handle / utterances of an offline one
   float* taps = nullptr;               // the current rate's prototype on the device (2 K q + 1 floats)
@@ -77,14 +79,15 @@ struct PcmFollow {
 
 // Caller samples -> 16 kHz float32.  grid (n_hops, rows).  in: [rows, n_hops * S] of the format; out: [rows, n_hops * 256].  hist_in / hist_out:
 // [rows][kPcmMaxHist]; they may be the same buffer when n_hops == 1.  active (device, [rows], may be null): a held row's history is not touched,
-// its input is not read, its output hop is zeros.  counts (device, [rows], may be null: every row has n_hops): the row's leading real hops, clamped
+// its input is not read, its output hop is zeros (the encode half in a G.711 format: the format's silence code).  counts (device, [rows], may be null: every row has n_hops): the row's leading real hops, clamped
 // by the kernel to 0 .. n_hops -- the hops behind a count are zeros and their input is not read, the new history is that of the last real hop,
 // and a row of count 0 has its history copied from hist_in to hist_out (with counts the two must be different buffers).
+// fmt: kPcmFmtF32 or kPcmFmtS16 at every rate, kPcmFmtUlaw or kPcmFmtAlaw at 8000 alone -- anything else is hipErrorInvalidValue.
 hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
+                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s);
 // 16 kHz float32 -> caller samples; the same conventions the other way round.
 hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int s16, int rows, int n_hops, hipStream_t s);
+                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s);
 // The same two with the upper band (rate_hz 32000 or 48000, else hipErrorInvalidValue): other kernels, the ones above are not touched.
 hipError_t launch_pcm_decode_upper(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s);

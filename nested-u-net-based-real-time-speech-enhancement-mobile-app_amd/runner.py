@@ -60,6 +60,9 @@ ABI_SYMBOLS = (
     "nutls_set_pcm_upper_follow", "nutls_pcm_upper_follow", "nutls_pcm_follow_gain",
     "nutls_set_atten_limit", "nutls_atten_limit", "nutls_istft_block_mix",
 )
+# ... and the declared symbols whose names carry a digit, listed apart: tests/test_abi.py compares ABI_SYMBOLS with the names it finds in
+# the header by a pattern of lower-case letters and underscores, which cannot see these
+ABI_SYMBOLS_G711 = ("nutls_pcm_g711_expand", "nutls_pcm_g711_compress")
 
 
 def load_library(path: Optional[str] = None) -> ctypes.CDLL:
@@ -174,6 +177,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_set_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
         lib.nutls_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
         lib.nutls_istft_block_mix.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_pcm_g711_expand"):
+        lib.nutls_pcm_g711_expand.argtypes = [c.c_int, c.POINTER(c.c_short), c.c_int]
+        lib.nutls_pcm_g711_compress.argtypes = [c.c_int, c.POINTER(c.c_short), c.POINTER(c.c_ubyte), c.c_size_t]
     lib.nutls_create_offline.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
     if not dev_lib or hasattr(lib, "nutls_create_offline_batch"):
         lib.nutls_create_offline_batch.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_void_p)]
@@ -195,7 +201,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.nutls_fused_pack_blob_plan.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_int, fp, c.c_size_t]
     lib.nutls_last_error.restype = c.c_char_p
     lib.nutls_version.restype = c.c_char_p
-    for name in ABI_SYMBOLS:
+    for name in ABI_SYMBOLS + ABI_SYMBOLS_G711:
         if dev_lib and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -248,6 +254,42 @@ def pcm_filter(rate: int, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
     return taps
 
 
+# G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW; 8000 Hz only): the codec names, their format codes and the silence code of each -- what a zero
+# hop compresses to, and what pads a recording and stands where the other formats have zeros
+G711_CODECS = {"ulaw": 2, "alaw": 3}
+G711_SILENCE = {"ulaw": 0xFF, "alaw": 0xD5}
+
+
+def _g711_format(codec) -> int:
+    if not isinstance(codec, str) or codec not in G711_CODECS:
+        raise ValueError("codec must be 'ulaw' or 'alaw', got %r" % (codec,))
+    return G711_CODECS[codec]
+
+
+def g711_expand(codec: str, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
+    """The int16 value of each of the 256 codes of ``codec`` ("ulaw" or "alaw"), ``[256]`` int16: ``table[c]`` is what the PCM gateway's
+    decode makes of byte ``c`` before it scales by 1 / 32768 (``nutls_pcm_g711_expand``).  Host only: needs no GPU."""
+    fmt = _g711_format(codec)
+    lib = lib or load_library()
+    table = np.empty(256, np.int16)
+    _check(lib, lib.nutls_pcm_g711_expand(fmt, table.ctypes.data_as(ctypes.POINTER(ctypes.c_short)), 256))
+    return table
+
+
+def g711_compress(codec: str, samples, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
+    """The codes of ``codec`` ("ulaw" or "alaw") for an int16 array of any shape -> uint8 array of that shape: what the PCM gateway's encode
+    makes of the int16 value it has quantised a sample to (``nutls_pcm_g711_compress``).  Host only: needs no GPU."""
+    fmt = _g711_format(codec)
+    x = np.asarray(samples)
+    if x.dtype != np.int16:
+        raise ValueError("samples must be int16, got %s" % x.dtype.name)
+    x = np.ascontiguousarray(x)
+    lib = lib or load_library()
+    out = np.empty(x.shape, np.uint8)
+    _check(lib, lib.nutls_pcm_g711_compress(fmt, x.ctypes.data_as(ctypes.POINTER(ctypes.c_short)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), x.size))
+    return out
+
+
 def atten_limit_from_db(db) -> np.float32:
     """The attenuation limit ``l`` of a cap of ``db`` decibels on the noise removed: ``float32(10 ** (-db / 20))``; 0 dB -> 1 (nothing is
     removed), ``None`` -> 0 (no cap: the model's full suppression).  ``ValueError``: a negative or NaN value."""
@@ -296,18 +338,27 @@ class _PcmFormat:
         _check(self._lib, self._lib.nutls_atten_limit(self._h, _fptr(a), len(a)))
         return a
 
-    _PCM_FORMATS = {"float32": 0, "int16": 1}
-    pcm_rate, pcm_dtype = 16000, "float32"
+    _PCM_FORMATS = {"float32": 0, "int16": 1, "ulaw": 2, "alaw": 3}
+    pcm_rate, pcm_dtype, pcm_codec = 16000, "float32", None
 
     def set_pcm_format(self, rate: int = 16000, dtype="float32") -> None:
         """What the ``_pcm`` methods take and return from now on: ``rate`` 8000, 16000, 32000 or 48000, ``dtype`` "float32" or "int16"
-        (32768 = 1.0).  May be called between any two hops; every stream's resampler history restarts from zeros and the upper band
-        (``set_pcm_upper_band``) is off again.  The other methods keep taking float32 at 16 kHz."""
-        name = np.dtype(dtype).name
+        (32768 = 1.0) -- or, at 8000 only, "ulaw" or "alaw": G.711, one byte per sample, which the ``_pcm`` methods take and return as
+        ``uint8`` arrays / ``torch.uint8`` tensors (``pcm_dtype`` is then "uint8" and ``pcm_codec`` the law; held rows and hops behind a
+        count come back as the law's silence code, 0xFF / 0xD5, not as zero bytes).  May be called between any two hops; every stream's
+        resampler history restarts from zeros and the upper band (``set_pcm_upper_band``) is off again.  The other methods keep taking
+        float32 at 16 kHz.  ``ValueError``: another rate or dtype, a G.711 law at a rate other than 8000 -- nothing changes."""
+        name = dtype if isinstance(dtype, str) and dtype in G711_CODECS else np.dtype(dtype).name
         if name not in self._PCM_FORMATS:
-            raise ValueError("dtype must be float32 or int16, got %s" % name)
+            raise ValueError("dtype must be float32, int16, 'ulaw' or 'alaw', got %s" % name)
         _check(self._lib, self._lib.nutls_set_pcm_format(self._h, int(rate), self._PCM_FORMATS[name]))
-        self.pcm_rate, self.pcm_dtype = int(rate), name
+        self.pcm_codec = name if name in G711_CODECS else None
+        self.pcm_rate, self.pcm_dtype = int(rate), "uint8" if self.pcm_codec else name
+
+    @property
+    def pcm_silence(self) -> int:
+        """The sample value of silence in the handle's format: 0, or the silence code of its G.711 law (0xFF / 0xD5)."""
+        return G711_SILENCE[self.pcm_codec] if self.pcm_codec else 0
 
     def set_pcm_upper_band(self, gain: float) -> None:
         """The band above 8 kHz of a 32 or 48 kHz caller, passed around the model and added back at ``gain`` in [0, 1], aligned with the
@@ -1186,13 +1237,13 @@ class NutlsOffline(_PcmFormat):
         return o
 
     def _wave_through_blocks(self, x: np.ndarray, lag: int, block) -> np.ndarray:
-        """``x [utterances, N]`` of the handle's sample type, padded with zeros to whole hops that cover ``N + lag`` samples, through
+        """``x [utterances, N]`` of the handle's sample type, padded with zeros (G.711: the silence code) to whole hops that cover ``N + lag`` samples, through
         ``block`` (array ``[utterances, n_hops * pcm_hop_samples]`` -> array of the same shape, n_hops <= max_frames) in blocks of
         ``max_frames`` hops; the first ``lag`` samples of the result are dropped, so that sample i of what is returned belongs to ``x[:, i]``."""
         S = self.pcm_hop_samples
         n = x.shape[1]
         hops = max(1, -(-(n + lag) // S))
-        padded = np.zeros((self.utterances, hops * S), x.dtype)
+        padded = np.full((self.utterances, hops * S), self.pcm_silence, x.dtype)
         padded[:, :n] = x
         out = np.empty_like(padded)
         for a in range(0, hops, self.max_frames):
@@ -1200,25 +1251,45 @@ class NutlsOffline(_PcmFormat):
             out[:, a * S:b * S] = block(np.ascontiguousarray(padded[:, a * S:b * S]))
         return out[:, lag:lag + n]
 
-    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge", upper_gain: float = 0.0, upper_follow: bool = False) -> np.ndarray:
+    @staticmethod
+    def _wave_format(dtype, rate, codec):
+        """What ``set_pcm_format`` is told for recordings of ``dtype`` at ``rate`` with ``codec``; ``ValueError`` for what does not go together.
+        A numpy dtype cannot say which law a byte array is in: uint8 needs ``codec``, and ``codec`` needs uint8 at 8000 Hz."""
+        name = np.dtype(dtype).name
+        if codec is None:
+            if name == "uint8":
+                raise ValueError("uint8 samples are G.711 codes: say which law with codec='ulaw' or codec='alaw'")
+            if name not in ("float32", "int16"):
+                raise ValueError("samples must be int16 or float32 (or uint8 with a codec), got %s" % name)
+            return name
+        _g711_format(codec)
+        if name != "uint8":
+            raise ValueError("codec=%r takes uint8 samples (G.711 codes), got %s" % (codec, name))
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) != 8000:
+            raise ValueError("codec=%r is G.711, which is 8 kHz: rate must be 8000, got %r" % (codec, rate))
+        return codec
+
+    def enhance_wave(self, wave, rate: int, dc_mode: str = "edge", codec: Optional[str] = None, upper_gain: float = 0.0,
+                     upper_follow: bool = False) -> np.ndarray:
         """A whole recording in its own format: ``wave [N]`` (one utterance) or ``[utterances, N]``, int16 or float32 numpy array of any
         length at ``rate`` (8000, 16000, 32000, 48000) -> the enhanced recording of the same shape and dtype, ALIGNED with the input:
         sample i of the result belongs to ``wave[i]`` (the input is padded with zeros to whole hops plus the total lag, one hop plus
         ``pcm_delay_samples``, and that lag is dropped from the front).  Sets the handle's format (``set_pcm_format``: the rate conversion
-        starts from a zero history); the model state carries on from earlier calls until :meth:`reset`.  ``upper_gain``: the gain of the band
+        starts from a zero history); the model state carries on from earlier calls until :meth:`reset`.  ``codec``: "ulaw" or "alaw" for a
+        uint8 array of G.711 codes at 8000 Hz (a dtype cannot say which law: required for uint8, ``ValueError`` with any other dtype or
+        rate); the padding is then the law's silence code, the result uint8 codes of the same law.  ``upper_gain``: the gain of the band
         above 8 kHz of a 32 or 48 kHz recording, passed around the model (``set_pcm_upper_band``, set after the format); 0.0: the result is
         band-limited to 8 kHz.  ``upper_follow``: that gain is the ceiling of one that follows the model's suppression
         (``set_pcm_upper_follow``, set after the gain)."""
         self._dc(dc_mode)
         x = np.asarray(wave)
-        if x.dtype.name not in self._PCM_FORMATS:
-            raise ValueError("wave must be int16 or float32, got %s" % x.dtype.name)
+        fmt = self._wave_format(x.dtype, rate, codec)
         batched = x.ndim == 2
         if x.ndim == 1 and self.utterances == 1:
             x = x[None]
         if x.ndim != 2 or x.shape[0] != self.utterances:
             raise ValueError("wave must be [%sN], got %s" % ("%d," % self.utterances if self.utterances > 1 else "", np.shape(wave)))
-        self.set_pcm_format(rate, x.dtype)
+        self.set_pcm_format(rate, fmt)
         self.set_pcm_upper_band(upper_gain)
         self.set_pcm_upper_follow(upper_follow)
         lag = self.pcm_hop_samples + self.pcm_delay_samples
@@ -1286,7 +1357,8 @@ class NutlsOffline(_PcmFormat):
         ``rate`` (8000, 16000, 32000, 48000): the recordings are in the callers' format, int16 or float32 arrays at that rate, all of one
         dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
         handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format, which turns the upper band
-        (``set_pcm_upper_band``) and with it its following gain (``set_pcm_upper_follow``) off: the results are band-limited to 8 kHz."""
+        (``set_pcm_upper_band``) and with it its following gain (``set_pcm_upper_follow``) off: the results are band-limited to 8 kHz.
+        uint8 arrays of G.711 codes are refused here (a dtype cannot say which law): :meth:`enhance_many_codec`."""
         return self._enhance_many(waves, dc_mode, rate, None)
 
     def enhance_many_atten(self, waves, atten_lim_db, dc_mode: str = "edge", rate: Optional[int] = None) -> List[np.ndarray]:
@@ -1300,6 +1372,26 @@ class NutlsOffline(_PcmFormat):
         if len(seq) != n:
             raise ValueError("atten_lim_db must be a scalar or one value per recording (%d), got %d" % (n, len(seq)))
         return self._enhance_many(waves, dc_mode, rate, [atten_limit_from_db(d) for d in seq])
+
+    def enhance_many_codec(self, waves, codec: str, dc_mode: str = "edge", rate: int = 8000, atten_lim_db=None) -> List[np.ndarray]:
+        """:meth:`enhance_many` for an archive of G.711 recordings: ``waves`` uint8 arrays ``[N_i]`` of codes of ONE law, ``codec`` "ulaw" or
+        "alaw" (a dtype cannot say which), ``rate`` 8000 -- the only rate G.711 has; anything else is a ``ValueError``, as is a dtype
+        other than uint8.  Each result is uint8 codes of the same law, has its input's length and is ALIGNED with it: what
+        ``enhance_wave(w, 8000, codec=codec)`` of a fresh one-utterance handle returns.  Recordings are padded with the law's silence code.
+        ``atten_lim_db``: as in :meth:`enhance_many_atten`, None for no cap on any recording.  (A method of its own, like
+        ``enhance_many_atten``: ``enhance_many`` keeps the signature it has, and refuses uint8 arrays.)"""
+        dc = self._dc(dc_mode)
+        waves = [np.asarray(w) for w in waves]
+        for w in waves:
+            self._wave_format(w.dtype, rate, codec)
+        self._wave_format(np.uint8, rate, codec)      # (an empty list: codec and rate are checked all the same)
+        limits = None
+        if atten_lim_db is not None:
+            seq = list(atten_lim_db) if isinstance(atten_lim_db, (list, tuple, np.ndarray)) else [atten_lim_db] * len(waves)
+            if len(seq) != len(waves):
+                raise ValueError("atten_lim_db must be a scalar or one value per recording (%d), got %d" % (len(waves), len(seq)))
+            limits = [atten_limit_from_db(d) for d in seq]
+        return self._enhance_many_pcm(waves, dc, int(rate), limits, codec)
 
     def _slot_limits(self, block, limits):
         """The scheduler's hand-over of :meth:`enhance_many_atten`: the slots of ``block`` that take a new recording get its limit."""
@@ -1335,27 +1427,28 @@ class NutlsOffline(_PcmFormat):
 
     _PCM_RATES = (8000, 16000, 32000, 48000)
 
-    def _enhance_many_pcm(self, waves, dc: int, rate, limits=None) -> List[np.ndarray]:
+    def _enhance_many_pcm(self, waves, dc: int, rate, limits=None, codec=None) -> List[np.ndarray]:
         """:meth:`enhance_many` in the callers' format.  Every recording is padded with zeros to whole hops that cover ``N + lag`` samples,
-        ``lag = pcm_hop_samples + pcm_delay_samples`` (the rule of :meth:`_wave_through_blocks`), and the lag is dropped from the front."""
+        ``lag = pcm_hop_samples + pcm_delay_samples`` (the rule of :meth:`_wave_through_blocks`), and the lag is dropped from the front.
+        ``codec`` (:meth:`enhance_many_codec`, which has checked dtype and rate): uint8 codes of that G.711 law, padded with its silence code."""
         waves = [np.asarray(w) for w in waves]
         if any(w.ndim != 1 for w in waves):
             raise ValueError("waves must be one-dimensional arrays")
         names = {w.dtype.name for w in waves}
-        if len(names) > 1 or not names <= set(self._PCM_FORMATS):
-            raise ValueError("with a rate, waves must all be int16 or all be float32, got %s" % sorted(names))
+        if codec is None and (len(names) > 1 or not names <= {"float32", "int16"}):
+            raise ValueError("with a rate, waves must all be int16 or all be float32 (uint8 G.711 codes: enhance_many_codec), got %s" % sorted(names))
         if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or int(rate) not in self._PCM_RATES:
             raise ValueError("rate must be 8000, 16000, 32000 or 48000, got %r" % (rate,))
         if not waves:
             return []
         dtype = waves[0].dtype
-        self.set_pcm_format(int(rate), dtype)
+        self.set_pcm_format(int(rate), codec or dtype)
         S = self.pcm_hop_samples
         lag = S + self.pcm_delay_samples
         hops = [max(1, -(-(len(w) + lag) // S)) for w in waves]
         padded = []
         for w, n in zip(waves, hops):
-            p = np.zeros(n * S, dtype)
+            p = np.full(n * S, self.pcm_silence, dtype)
             p[:len(w)] = w
             padded.append(p)
         outs = [np.empty_like(p) for p in padded]
