@@ -4,12 +4,12 @@
 // nutls_enhance_hop_active, nutls_enhance_block) on library buffers and encodes: the model path, the masks, hop fusion and the state
 // coherence are that code, not copies of it.  At 16000 / float32 the entries ARE the plain ones (forwarded before anything else happens).
 // The _pcm_ragged block entries do the same around nutls_enhance_block_ragged, with the per-utterance hop counts handed to both kernels.
-// Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): with a gain other than 0 decode_launch / encode_launch start the kernels that also
-// form and add the band above 8 kHz -- every entry below goes through those two, so every entry honours the gain; with 0 nothing here differs.
-// Follow (nutls_set_pcm_upper_follow): the same two launches start the kernels whose gain follows the model; off, nothing here differs.
+// Every launch of either half goes through half_launch, which picks the mode from the handle's settings -- so every entry honours them:
+// upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): with a gain other than 0 the launches also form and add the band above 8 kHz;
+// follow (nutls_set_pcm_upper_follow): on top of that, the gain follows the model.  With a gain of 0 / follow off nothing here differs.
 // G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8000 Hz only): a format like the others -- nutls_set_pcm_format validates it, sample_bytes is 1, the
-// two plain launchers get the format code; nothing else here knows.  The rule itself is stated once on the host (g711_expand / g711_compress below).
-// The kernels: pcm.hip.
+// launch gets the format code; nothing else here knows.  The rule itself is stated once on the host (g711_expand / g711_compress below).
+// The kernel template, its 36 instantiations and the one place that picks among them: pcm.hip.
 #include <cstdint>
 
 #include "engine.hpp"
@@ -24,7 +24,7 @@ bool g711_format(int fmt) { return fmt == NUTLS_PCM_ULAW || fmt == NUTLS_PCM_ALA
 size_t sample_bytes(const Engine* e) { return g711_format(e->pcm.fmt) ? 1 : e->pcm.fmt == NUTLS_PCM_S16 ? sizeof(short) : sizeof(float); }
 int max_hops(const Engine* e) { return e->offline ? e->offline : 1; }
 static_assert(NUTLS_PCM_F32 == kPcmFmtF32 && NUTLS_PCM_S16 == kPcmFmtS16 && NUTLS_PCM_ULAW == kPcmFmtUlaw && NUTLS_PCM_ALAW == kPcmFmtAlaw,
-              "the launchers of pcm.hpp take the format codes of nutls.h");
+              "PcmLaunch of pcm.hpp takes the format codes of nutls.h");
 
 // ---- G.711, the rule as nutls.h words it ("G.711"): what nutls_pcm_g711_expand / _compress return and what the kernels of pcm.hip agree with ----
 int g711_expand(int fmt, int c) {
@@ -79,12 +79,12 @@ int pcm_init(Engine* e) {
   st.rows = e->offline ? e->outt : e->B;
   const size_t hist = static_cast<size_t>(st.rows) * kPcmMaxHist;
   const size_t wave = static_cast<size_t>(st.rows) * max_hops(e) * NUTLS_FRAME_STEP;
+  if (int rc = dev_alloc_once(e, static_cast<size_t>(2 * kPcmK * kPcmMaxQ + 1), &st.taps, false)) return rc;
+  for (PcmHalf* half : {&st.dec, &st.enc})
+    for (float*& p : half->hist)
+      if (int rc = dev_alloc_once(e, hist, &p, true)) return rc;
   int rc;
-  if ((rc = dev_alloc_once(e, static_cast<size_t>(2 * kPcmK * kPcmMaxQ + 1), &st.taps, false)) || (rc = dev_alloc_once(e, hist, &st.hist_dec[0], true)) ||
-      (rc = dev_alloc_once(e, hist, &st.hist_dec[1], true)) || (rc = dev_alloc_once(e, hist, &st.hist_enc[0], true)) ||
-      (rc = dev_alloc_once(e, hist, &st.hist_enc[1], true)) || (rc = dev_alloc_once(e, wave, &st.f_in, true)) ||
-      (rc = dev_alloc_once(e, wave, &st.f_out, true)) || (rc = upload_taps(e)))
-    return rc;
+  if ((rc = dev_alloc_once(e, wave, &st.f_in, true)) || (rc = dev_alloc_once(e, wave, &st.f_out, true)) || (rc = upload_taps(e))) return rc;
   HIP_TRY(hipDeviceSynchronize());      // the zeroes are in place before a caller's stream reads them
   st.ready = true;
   return NUTLS_OK;
@@ -95,30 +95,28 @@ int upper_init(Engine* e) {
   PcmState& st = e->pcm;
   if (st.upper_ready) return NUTLS_OK;
   const size_t rows = static_cast<size_t>(st.rows);
-  int rc;
-  if ((rc = dev_alloc_once(e, rows * kPcmUpCtx, &st.up_ctx[0], true)) || (rc = dev_alloc_once(e, rows * kPcmUpCtx, &st.up_ctx[1], true)) ||
-      (rc = dev_alloc_once(e, rows * kPcmMaxHop, &st.up_last[0], true)) || (rc = dev_alloc_once(e, rows * kPcmMaxHop, &st.up_last[1], true)) ||
-      (rc = dev_alloc_once(e, rows * max_hops(e) * kPcmMaxHop, &st.up_u, true)))
-    return rc;
+  for (PcmHalf* half : {&st.dec, &st.enc})
+    for (float*& p : half->up)
+      if (int rc = dev_alloc_once(e, rows * half->up_stride, &p, true)) return rc;
+  if (int rc = dev_alloc_once(e, rows * max_hops(e) * kPcmMaxHop, &st.up_u, true)) return rc;
   st.upper_ready = true;
   return NUTLS_OK;
 }
 
-// Follow's buffers (nutls_set_pcm_upper_follow), allocated when follow is first enabled -- after upper_init.
+// Follow's buffers (nutls_set_pcm_upper_follow), allocated when follow is first enabled -- after upper_init.  The carry is the encode half's alone.
 int follow_init(Engine* e) {
   PcmState& st = e->pcm;
   if (st.follow_ready) return NUTLS_OK;
   const size_t rows = static_cast<size_t>(st.rows);
-  int rc;
-  if ((rc = dev_alloc_once(e, rows * max_hops(e), &st.fo_a, true)) || (rc = dev_alloc_once(e, rows * kPcmFollowCarry, &st.fo_carry[0], true)) ||
-      (rc = dev_alloc_once(e, rows * kPcmFollowCarry, &st.fo_carry[1], true)))
-    return rc;
+  if (int rc = dev_alloc_once(e, rows * max_hops(e), &st.fo_a, true)) return rc;
+  for (float*& p : st.enc.fo)
+    if (int rc = dev_alloc_once(e, rows * kPcmFollowCarry, &p, true)) return rc;
   st.follow_ready = true;
   return NUTLS_OK;
 }
 
-// Row idx's (< 0: every row's) resampler histories, upper-band and follow state, where they exist.  (up_u and fo_a are not state: the encode half reads only
-// what the decode half of the same hop or block wrote there.)
+// Row idx's (< 0: every row's) carried state in both halves -- resampler histories, upper band, follow --, where it exists.  (up_u and fo_a are
+// not state: the encode half reads only what the decode half of the same hop or block wrote there.)
 int zero_histories(Engine* e, int idx) {
   PcmState& st = e->pcm;
   if (!st.ready) return NUTLS_OK;
@@ -127,57 +125,47 @@ int zero_histories(Engine* e, int idx) {
     else HIP_TRY(hipMemset(p + static_cast<size_t>(idx) * stride, 0, stride * sizeof(float)));
     return NUTLS_OK;
   };
-  for (float* p : {st.hist_dec[0], st.hist_dec[1], st.hist_enc[0], st.hist_enc[1]})
-    if (int rc = zero(p, kPcmMaxHist)) return rc;
-  if (!st.upper_ready) return NUTLS_OK;
-  for (int i = 0; i < 2; ++i) {
-    if (int rc = zero(st.up_ctx[i], kPcmUpCtx)) return rc;
-    if (int rc = zero(st.up_last[i], kPcmMaxHop)) return rc;
-  }
-  if (!st.follow_ready) return NUTLS_OK;
-  for (int i = 0; i < 2; ++i)
-    if (int rc = zero(st.fo_carry[i], kPcmFollowCarry)) return rc;
+  for (PcmHalf* half : {&st.dec, &st.enc})
+    for (int i = 0; i < 2; ++i) {
+      if (int rc = zero(half->hist[i], kPcmMaxHist)) return rc;
+      if (st.upper_ready)
+        if (int rc = zero(half->up[i], half->up_stride)) return rc;
+      if (st.follow_ready && half->fo[i])      // (follow is enabled under a gain other than 0 only: the upper band's buffers exist)
+        if (int rc = zero(half->fo[i], kPcmFollowCarry)) return rc;
+    }
   return NUTLS_OK;
 }
 
-// One launch of a half.  A block call (offline handle) flips the history buffers; a hop call (streaming handle) works in place on buffer 0.
-// counts: the DEVICE counts of a ragged block or null (the flip is the whole handle's: the kernel carries a held row's history across).
-// With the upper band on (a gain other than 0) the launch is the kernel that also forms / adds it; its carried state flips with the histories.
-// With follow on top it is the kernel whose gain follows the model; follow's carried state is the encode half's and flips with enc_par.
-int decode_launch(Engine* e, const void* in, float* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
+// One launch of a half.  A block call (offline handle) flips the half's buffers -- histories, upper-band and follow carry alike: one parity --;
+// a hop call (streaming handle) works in place on buffer 0.  counts: the DEVICE counts of a ragged block or null (the flip is the whole
+// handle's: the kernel carries a held row's state across).  The mode is the handle's: with the upper band on (a gain other than 0) the launch
+// also forms / adds it, with follow on top its gain follows the model.
+int half_launch(Engine* e, PcmDir dir, const void* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
   PcmState& st = e->pcm;
+  PcmHalf& half = st.half(dir);
   if (int rc = enqueue_on(e, s)) return rc;
-  const int par = st.dec_par, nxt = e->offline ? 1 - par : par;
-  if (st.upper != 0.f && st.follow) {
-    const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
-    const PcmFollow fo = {st.fo_a, nullptr, nullptr};
-    HIP_TRY(launch_pcm_decode_follow(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, fo, s));
-  } else if (st.upper != 0.f) {
-    const PcmUpper ub = {st.upper, st.up_u, st.up_ctx[par], st.up_ctx[nxt]};
-    HIP_TRY(launch_pcm_decode_upper(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
-  } else {
-    HIP_TRY(launch_pcm_decode(in, out, st.taps, st.hist_dec[par], st.hist_dec[nxt], active, counts, st.rate, st.fmt, st.rows, n_hops, s));
+  const int par = half.par, nxt = e->offline ? 1 - par : par;
+  PcmLaunch L = {in, out, st.taps, half.hist[par], half.hist[nxt], active, counts, st.rate, st.fmt, st.rows, n_hops, PcmMode::kPlain, {}, {}};
+  if (st.upper != 0.f) {
+    L.mode = st.follow ? PcmMode::kFollow : PcmMode::kUpper;
+    L.ub = {st.upper, st.up_u, half.up[par], half.up[nxt]};
+    if (st.follow) L.fo = {st.fo_a, half.fo[par], half.fo[nxt]};
   }
-  st.dec_par = nxt;
+  HIP_TRY(launch_pcm(dir, L, s));
+  half.par = nxt;
   return NUTLS_OK;
 }
 
-int encode_launch(Engine* e, const float* in, void* out, const unsigned char* active, int n_hops, hipStream_t s, const int* counts = nullptr) {
-  PcmState& st = e->pcm;
-  if (int rc = enqueue_on(e, s)) return rc;
-  const int par = st.enc_par, nxt = e->offline ? 1 - par : par;
-  if (st.upper != 0.f && st.follow) {
-    const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
-    const PcmFollow fo = {st.fo_a, st.fo_carry[par], st.fo_carry[nxt]};
-    HIP_TRY(launch_pcm_encode_follow(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, fo, s));
-  } else if (st.upper != 0.f) {
-    const PcmUpper ub = {st.upper, st.up_u, st.up_last[par], st.up_last[nxt]};
-    HIP_TRY(launch_pcm_encode_upper(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt == NUTLS_PCM_S16, st.rows, n_hops, ub, s));
-  } else {
-    HIP_TRY(launch_pcm_encode(in, out, st.taps, st.hist_enc[par], st.hist_enc[nxt], active, counts, st.rate, st.fmt, st.rows, n_hops, s));
-  }
-  st.enc_par = nxt;
-  return NUTLS_OK;
+// the handle's device is current and the gateway's buffers exist
+int pcm_ready(Engine* e) {
+  HIP_TRY(hipSetDevice(e->device));
+  return pcm_init(e);
+}
+
+// what the entries of one half on its own do behind their refusals
+int half_entry(nutls_handle* h, PcmDir dir, const void* in, void* out, const unsigned char* active, int n_hops, void* stream, const int* counts = nullptr) {
+  if (int rc = pcm_ready(&h->eng)) return rc;
+  return half_launch(&h->eng, dir, in, out, active, n_hops, static_cast<hipStream_t>(stream), counts);
 }
 
 // the _host entries' staging of the callers' samples
@@ -220,21 +208,45 @@ int hop_refusals(nutls_handle* h, const unsigned char* active, int dc_mode, cons
 // decode -> nutls_enhance_hop(_active) on the library's float buffers -> encode (active: device mask or null)
 int hop_device(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
   Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
+  if (int rc = pcm_ready(e)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, active, 1, s)) return rc;
+  if (int rc = half_launch(e, PcmDir::kDecode, pcm_in, e->pcm.f_in, active, 1, s)) return rc;
   if (int rc = nutls_enhance_hop_active(h, e->pcm.f_in, e->pcm.f_out, active, dc_mode, stream)) return rc;
-  return encode_launch(e, e->pcm.f_out, pcm_out, active, 1, s);
+  return half_launch(e, PcmDir::kEncode, e->pcm.f_out, pcm_out, active, 1, s);
 }
 
-// The callers' samples to the library's staging, hop_device on the library's stream, the results back, one synchronisation (active: HOST mask
-// or null).  The mask is handed on as a device mask: the library does not follow it through nutls_state_set's bookkeeping as the float _host
-// entries do (nutls.h, nutls_step_active: the more expensive launches then last until one call steps all streams).
+// decode -> nutls_enhance_block(_ragged) on the library's float buffers -> encode.  hops: the DEVICE counts of a ragged block, handed to all
+// three parts, or null.  With counts the decode writes zero hops behind them into the library's buffer, nutls_enhance_block_ragged reads none
+// of them and writes zeros there, the encode reads none of those.
+int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  if (int rc = pcm_ready(e)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = half_launch(e, PcmDir::kDecode, pcm_in, e->pcm.f_in, nullptr, n_hops, s, hops)) return rc;
+  if (int rc = nutls_enhance_block_ragged(h, e->pcm.f_in, e->pcm.f_out, n_hops, hops, dc_mode, stream)) return rc;      // (null hops: nutls_enhance_block)
+  return half_launch(e, PcmDir::kEncode, e->pcm.f_out, pcm_out, nullptr, n_hops, s, hops);
+}
+
+// What the _host entries share, on the library's stream (the entry has put it behind what earlier calls queued on the callers' streams):
+// `samples` of the callers' format to the library's staging, device_path(staged in, staged out) on that stream, the results back, one
+// synchronisation.
+template <typename F>
+int through_staging(Engine* e, const void* pcm_in, void* pcm_out, size_t samples, F device_path) {
+  const size_t bytes = samples * sample_bytes(e);
+  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = device_path(e->pcm.raw_in, e->pcm.raw_out)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  enqueue_idle(e);
+  return NUTLS_OK;
+}
+
+// hop_device through the staging (active: HOST mask or null).  The mask is handed on as a device mask: the library does not follow it through
+// nutls_state_set's bookkeeping as the float _host entries do (nutls.h, nutls_step_active: the more expensive launches then last until one
+// call steps all streams).
 int hop_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode) {
   Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
+  if (int rc = pcm_ready(e)) return rc;
   if (int rc = raw_init(e)) return rc;
   if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
   const unsigned char* d_act = nullptr;
@@ -243,35 +255,16 @@ int hop_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned 
     HIP_TRY(hipMemcpyAsync(e->pcm.d_active, active, static_cast<size_t>(e->B), hipMemcpyHostToDevice, e->stream));
     d_act = e->pcm.d_active;
   }
-  const size_t bytes = static_cast<size_t>(e->B) * hop_samples(e) * sample_bytes(e);
-  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
-  if (int rc = hop_device(h, e->pcm.raw_in, e->pcm.raw_out, d_act, dc_mode, e->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  enqueue_idle(e);
-  return NUTLS_OK;
+  return through_staging(e, pcm_in, pcm_out, static_cast<size_t>(e->B) * hop_samples(e),
+                         [&](const void* in, void* out) { return hop_device(h, in, out, d_act, dc_mode, e->stream); });
 }
 
-int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode, void* stream) {
+// block_device through the staging (hops: DEVICE counts or null; with counts the rows behind them cross the link too: the kernels do not read
+// them on the device)
+int block_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode) {
   Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, nullptr, n_hops, s)) return rc;
-  if (int rc = nutls_enhance_block(h, e->pcm.f_in, e->pcm.f_out, n_hops, dc_mode, stream)) return rc;
-  return encode_launch(e, e->pcm.f_out, pcm_out, nullptr, n_hops, s);
-}
-
-// The ragged block: the three parts of block_device, each with the DEVICE counts `hops` (not null).  The decode writes zero hops behind the
-// counts into the library's buffer, nutls_enhance_block_ragged reads none of them and writes zeros there, the encode reads none of those.
-int block_device_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = decode_launch(e, pcm_in, e->pcm.f_in, nullptr, n_hops, s, hops)) return rc;
-  if (int rc = nutls_enhance_block_ragged(h, e->pcm.f_in, e->pcm.f_out, n_hops, hops, dc_mode, stream)) return rc;
-  return encode_launch(e, e->pcm.f_out, pcm_out, nullptr, n_hops, s, hops);
+  return through_staging(e, pcm_in, pcm_out, static_cast<size_t>(e->outt) * n_hops * hop_samples(e),
+                         [&](const void* in, void* out) { return block_device(h, in, out, n_hops, hops, dc_mode, e->stream); });
 }
 
 // the 16-byte alignment nutls.h asks of every _pcm buffer is checked where counts come with it, as the ragged float entries do
@@ -413,7 +406,7 @@ int nutls_pcm_follow_gain(nutls_handle* h, float* gains, int n) {
   if (n != e->pcm.rows) return fail(NUTLS_ERR_ARG, "nutls_pcm_follow_gain: n must be the handle's rows, " + std::to_string(e->pcm.rows));
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());      // the encode launches queued on the callers' streams have written what is read here
-  HIP_TRY(hipMemcpy2D(gains, sizeof(float), e->pcm.fo_carry[e->pcm.enc_par] + kPcmFollowGainAt, kPcmFollowCarry * sizeof(float), sizeof(float),
+  HIP_TRY(hipMemcpy2D(gains, sizeof(float), e->pcm.enc.fo[e->pcm.enc.par] + kPcmFollowGainAt, kPcmFollowCarry * sizeof(float), sizeof(float),
                       static_cast<size_t>(n), hipMemcpyDeviceToHost));
   return NUTLS_OK;
 }
@@ -461,18 +454,12 @@ int nutls_enhance_hop_pcm_host_active(nutls_handle* h, const void* pcm_in, void*
 // The two halves on their own (at 16000 / float32: copies).  They need no model, so a mask is taken on every streaming handle.
 int nutls_pcm_decode_hop(nutls_handle* h, const void* pcm_in, float* hop_out, const unsigned char* active, void* stream) {
   if (int rc = hop_args(h, pcm_in && hop_out, "nutls_pcm_decode_hop")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return decode_launch(e, pcm_in, hop_out, active, 1, static_cast<hipStream_t>(stream));
+  return half_entry(h, PcmDir::kDecode, pcm_in, hop_out, active, 1, stream);
 }
 
 int nutls_pcm_encode_hop(nutls_handle* h, const float* hop_in, void* pcm_out, const unsigned char* active, void* stream) {
   if (int rc = hop_args(h, hop_in && pcm_out, "nutls_pcm_encode_hop")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return encode_launch(e, hop_in, pcm_out, active, 1, static_cast<hipStream_t>(stream));
+  return half_entry(h, PcmDir::kEncode, hop_in, pcm_out, active, 1, stream);
 }
 
 // ---- offline handles --------------------------------------------------------------------------------------------------------------------------
@@ -480,7 +467,7 @@ int nutls_enhance_block_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, 
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_pcm")) return rc;
   if (plain_format(&h->eng)) return nutls_enhance_block(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode, stream);
   if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm")) return rc;
-  return block_device(h, pcm_in, pcm_out, n_hops, dc_mode, stream);
+  return block_device(h, pcm_in, pcm_out, n_hops, nullptr, dc_mode, stream);
 }
 
 int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode) {
@@ -488,33 +475,20 @@ int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_
   if (plain_format(&h->eng)) return nutls_enhance_block_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode);
   if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm_host")) return rc;
   Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
+  if (int rc = pcm_ready(e)) return rc;
   if (int rc = raw_init(e)) return rc;
-  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * hop_samples(e) * sample_bytes(e);
   if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
-  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
-  if (int rc = block_device(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, dc_mode, e->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  enqueue_idle(e);
-  return NUTLS_OK;
+  return block_host(h, pcm_in, pcm_out, n_hops, nullptr, dc_mode);
 }
 
 int nutls_pcm_decode_block(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, void* stream) {
   if (int rc = block_args(h, pcm_in && wave_out, n_hops, "nutls_pcm_decode_block")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return decode_launch(e, pcm_in, wave_out, nullptr, n_hops, static_cast<hipStream_t>(stream));
+  return half_entry(h, PcmDir::kDecode, pcm_in, wave_out, nullptr, n_hops, stream);
 }
 
 int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, void* stream) {
   if (int rc = block_args(h, wave_in && pcm_out, n_hops, "nutls_pcm_encode_block")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return encode_launch(e, wave_in, pcm_out, nullptr, n_hops, static_cast<hipStream_t>(stream));
+  return half_entry(h, PcmDir::kEncode, wave_in, pcm_out, nullptr, n_hops, stream);
 }
 
 // ---- offline handles, ragged: per-utterance hop counts in the callers' format ------------------------------------------------------------------
@@ -527,7 +501,7 @@ int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pc
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;
   if (int rc = dc_ok(dc_mode, who)) return rc;
   if (int rc = aligned16(pcm_in, pcm_out, who)) return rc;
-  return block_device_ragged(h, pcm_in, pcm_out, n_hops, hops, dc_mode, stream);
+  return block_device(h, pcm_in, pcm_out, n_hops, hops, dc_mode, stream);
 }
 
 // hops: HOST.  Every refusal, the counts' included, comes before the first conversion: a refused call leaves the histories where they were.
@@ -540,37 +514,24 @@ int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, voi
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;
   if (int rc = dc_ok(dc_mode, who)) return rc;
   Engine* e = &h->eng;
-  if (int rc = upload_counts(e, hops, n_hops, who)) return rc;
+  if (int rc = upload_counts(e, hops, n_hops, who)) return rc;      // (sets the device, puts the library's stream behind the earlier calls)
   if (int rc = pcm_init(e)) return rc;
   if (int rc = raw_init(e)) return rc;
-  // (the rows behind the counts cross the link too: the kernels do not read them on the device)
-  const size_t bytes = static_cast<size_t>(e->outt) * n_hops * hop_samples(e) * sample_bytes(e);
-  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
-  if (int rc = block_device_ragged(h, e->pcm.raw_in, e->pcm.raw_out, n_hops, e->d_counts, dc_mode, e->stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  enqueue_idle(e);
-  return NUTLS_OK;
+  return block_host(h, pcm_in, pcm_out, n_hops, e->d_counts, dc_mode);
 }
 
 int nutls_pcm_decode_block_ragged(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, const int* hops, void* stream) {
   if (!hops) return nutls_pcm_decode_block(h, pcm_in, wave_out, n_hops, stream);
   if (int rc = block_args(h, pcm_in && wave_out, n_hops, "nutls_pcm_decode_block_ragged")) return rc;
   if (int rc = aligned16(pcm_in, wave_out, "nutls_pcm_decode_block_ragged")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return decode_launch(e, pcm_in, wave_out, nullptr, n_hops, static_cast<hipStream_t>(stream), hops);
+  return half_entry(h, PcmDir::kDecode, pcm_in, wave_out, nullptr, n_hops, stream, hops);
 }
 
 int nutls_pcm_encode_block_ragged(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, const int* hops, void* stream) {
   if (!hops) return nutls_pcm_encode_block(h, wave_in, pcm_out, n_hops, stream);
   if (int rc = block_args(h, wave_in && pcm_out, n_hops, "nutls_pcm_encode_block_ragged")) return rc;
   if (int rc = aligned16(wave_in, pcm_out, "nutls_pcm_encode_block_ragged")) return rc;
-  Engine* e = &h->eng;
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = pcm_init(e)) return rc;
-  return encode_launch(e, wave_in, pcm_out, nullptr, n_hops, static_cast<hipStream_t>(stream), hops);
+  return half_entry(h, PcmDir::kEncode, wave_in, pcm_out, nullptr, n_hops, stream, hops);
 }
 
 }  // extern "C"

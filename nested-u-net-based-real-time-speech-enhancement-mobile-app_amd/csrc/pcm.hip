@@ -1,7 +1,8 @@
 // PCM gateway: the callers' samples (float32 or int16 at 8 / 16 / 32 / 48 kHz) to and from the library's float32 at 16 kHz (nutls_set_pcm_format).
 //
-// Two kernels, decode and encode, each one 256-thread workgroup per (row, hop) -- row = stream of a streaming handle, utterance of an offline
-// one; the hop entries launch them with one hop per row, the block entries with n_hops.  Both run the same body:
+// One device body (pcm_hop) behind one kernel template (pcm_kernel), instantiated 36 times -- per half (decode, encode), rate, sample type and
+// mode: launch_half, below, is the one place that says which exist and picks one.  A launch is one 256-thread workgroup per (row, hop) -- row =
+// stream of a streaming handle, utterance of an offline one; the hop entries launch one hop per row, the block entries n_hops.  The body:
 //   1. the prototype p[0 .. 2 K q] and the hop with its left context (the last 2 K q samples in front of it for a rate reduction, the last 2 K
 //      for a rate increase) go to LDS as float32, 16 bytes per lane and load (8 int16 or 4 float32).  The context of a row's first hop comes
 //      from the history the handle keeps, that of the later hops of a block straight from the row;
@@ -15,8 +16,8 @@
 // of hop k - 1 writes the history, a hop behind k returns before 1. with a zero hop; k == 0 holds the row, and because a block call flips the
 // history buffers of the whole handle, the workgroup of its hop 0 copies the row's history across.
 // Cost: 256 * 145 FMAs per stream and hop at most (48 kHz decode); the launch, not the arithmetic, is what a hop pays for.
-// Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): the band above 8 kHz goes around the model inside the same two launches, in two more
-// kernels of the same body (pcm_hop<..., UPPER>, see there) -- the kernels above are the ones a gain of 0 runs.  Per caller sample n of a stream,
+// Upper band (nutls_set_pcm_upper_band, 32 / 48 kHz): the band above 8 kHz goes around the model inside the same two launches, in the
+// instantiations with UPPER (pcm_hop<..., UPPER>, see there) -- the ones without are what a gain of 0 runs.  Per caller sample n of a stream,
 // each a fixed sequence of fp32 operations wherever the hop or block boundary falls:
 //   d[m]   = the decode chain: taps ascending, one FMA each, from 0                                      (2 K q + 1 FMAs)
 //   c[n]   = the encode chain over d: taps r, r + q, ... ascending, one FMA each, from 0, WITHOUT its product by q   (2 K + 1 FMAs at r = 0, else 2 K)
@@ -25,11 +26,10 @@
 //   out[n] = fmaf(gain, u[n - S], z[n])                                                                    (one FMA)
 // The longest path of an output sample has 2 K q + 2 K + 4 roundings (d, c, u, out).  +49 FMAs per caller sample in the decode, and the 2 K
 // decoded samples of context computed again by every hop of a block but its first (+19 % of the decode chains); the encode adds one FMA.
-// Follow (nutls_set_pcm_upper_follow): the gain of out[n] follows the model, gamma_t[n] of nutls.h -- two more kernels again (pcm_hop<..., UPPER,
+// Follow (nutls_set_pcm_upper_follow): the gain of out[n] follows the model, gamma_t[n] of nutls.h -- the instantiations with FOLLOW (pcm_hop<..., UPPER,
 // FOLLOW>), in the same two launches; one energy code for both halves (pcm_e2), every g a function of 5 a and 5 b, so one workgroup per (row, hop).
 // G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8 kHz only): two more sample types beside float32 and int16, one byte per sample (ulaw_t, alaw_t), so
-// four more kernels of the same body -- the 8 kHz decode and encode of each law; no other rate has them, and the kernels above are what the
-// other formats run.  A lane loads or stores 16 codes in its 16 bytes.  On the way in a code is expanded to its int16 value and that times
+// four instantiations -- the 8 kHz decode and encode of each law; no other rate and no other mode has them.  A lane loads or stores 16 codes in its 16 bytes.  On the way in a code is expanded to its int16 value and that times
 // 2^-15 (exact): from there on the chain is the int16 format's.  On the way out the float is quantised by to_s16, the int16 format's rule,
 // and that value is compressed.  Both directions are integer bit operations (g711_expand, g711_compress: the segment of a sample from the
 // position of its leading bit, no table), exact, and agree with the host's statement of the rule (nutls_pcm_g711_expand / _compress, api_pcm.cpp)
@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "pcm.hpp"
 
@@ -409,60 +410,77 @@ __device__ __forceinline__ void pcm_hop(const TI* in, TO* out, const float* taps
   }
 }
 
-// caller samples -> 16 kHz float32: a rate above 16 kHz is reduced, 8 kHz is doubled
-template <int Q, bool UP, typename TI>
-__global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
-                                                              const unsigned char* active, const int* counts, int n_hops) {
-  pcm_hop<Q, UP, UP ? 256 / Q : 256 * Q, TI, float>(in, out, taps, hist_in, hist_out, active, counts, n_hops);
+// The one kernel: a workgroup is one pcm_hop.  ub / fo are read by the instantiations with UPPER / FOLLOW alone.
+template <int Q, bool UP, int NIN, typename TI, typename TO, bool UPPER, bool FOLLOW>
+__global__ __launch_bounds__(kThreads) void pcm_kernel(const TI* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
+                                                       const unsigned char* active, const int* counts, int n_hops, PcmUpper ub, PcmFollow fo) {
+  pcm_hop<Q, UP, NIN, TI, TO, UPPER, FOLLOW>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo);
 }
 
-// 16 kHz float32 -> caller samples
-template <int Q, bool UP, typename TO>
-__global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
-                                                              const unsigned char* active, const int* counts, int n_hops) {
-  pcm_hop<Q, UP, 256, float, TO>(in, out, taps, hist_in, hist_out, active, counts, n_hops);
+// ---- which instantiation a launch runs: each run-time value becomes a compile-time one in one place, and f is called with it ---------------------
+template <typename F>
+hipError_t with_rate(int rate_hz, F f) {
+  switch (rate_hz) {
+    case 8000: return f(std::integral_constant<int, 8000>{});
+    case 16000: return f(std::integral_constant<int, 16000>{});
+    case 32000: return f(std::integral_constant<int, 32000>{});
+    case 48000: return f(std::integral_constant<int, 48000>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+// (Q, UP) of a rate: the decode half reduces a rate above 16 kHz and doubles 8 kHz, the encode half undoes that
+template <int HZ, bool ENC>
+struct Resample {
+  static constexpr int q = HZ == 16000 ? 1 : HZ == 48000 ? 3 : 2;
+  static constexpr bool up = ENC ? HZ > 16000 : HZ < 16000;
+};
+
+template <typename F>
+hipError_t with_sample_type(int fmt, F f) {
+  switch (fmt) {
+    case kPcmFmtF32: return f(float{});
+    case kPcmFmtS16: return f(short{});
+    case kPcmFmtUlaw: return f(ulaw_t{});
+    case kPcmFmtAlaw: return f(alaw_t{});
+    default: return hipErrorInvalidValue;
+  }
 }
 
-// The two with the upper band: rates above 16 kHz only (decode reduces, encode increases)
-template <int Q, typename TI>
-__global__ __launch_bounds__(kThreads) void pcm_decode_upper_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
-                                                                    const unsigned char* active, const int* counts, int n_hops, PcmUpper ub) {
-  pcm_hop<Q, false, 256 * Q, TI, float, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub);
+template <typename F>
+hipError_t with_mode(PcmMode mode, F f) {      // f(UPPER, FOLLOW)
+  switch (mode) {
+    case PcmMode::kPlain: return f(std::false_type{}, std::false_type{});
+    case PcmMode::kUpper: return f(std::true_type{}, std::false_type{});
+    case PcmMode::kFollow: return f(std::true_type{}, std::true_type{});
+    default: return hipErrorInvalidValue;
+  }
 }
 
-template <int Q, typename TO>
-__global__ __launch_bounds__(kThreads) void pcm_encode_upper_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
-                                                                    const unsigned char* active, const int* counts, int n_hops, PcmUpper ub) {
-  pcm_hop<Q, true, 256, float, TO, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub);
-}
-
-// The two with the upper band's gain following the model
-template <int Q, typename TI>
-__global__ __launch_bounds__(kThreads) void pcm_decode_follow_kernel(const TI* in, float* out, const float* taps, const float* hist_in, float* hist_out,
-                                                                     const unsigned char* active, const int* counts, int n_hops, PcmUpper ub, PcmFollow fo) {
-  pcm_hop<Q, false, 256 * Q, TI, float, true, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo);
-}
-
-template <int Q, typename TO>
-__global__ __launch_bounds__(kThreads) void pcm_encode_follow_kernel(const float* in, TO* out, const float* taps, const float* hist_in, float* hist_out,
-                                                                     const unsigned char* active, const int* counts, int n_hops, PcmUpper ub, PcmFollow fo) {
-  pcm_hop<Q, true, 256, float, TO, true, true>(in, out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo);
-}
-
-template <int Q, bool UP, typename T>
-hipError_t decode_as(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                     const int* counts, int rows, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL((pcm_decode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out,
-                     active, counts, n_hops);
-  return hipGetLastError();
-}
-
-template <int Q, bool UP, typename T>
-hipError_t encode_as(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                     const int* counts, int rows, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL((pcm_encode_kernel<Q, UP, T>), dim3(n_hops, rows), dim3(kThreads), 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out,
-                     active, counts, n_hops);
-  return hipGetLastError();
+// The 36 kernels: 16 plain (4 rates x float32 / int16 x 2 halves), 4 G.711 (8 kHz, 2 laws x 2 halves), 8 with the upper band (32 / 48 kHz x
+// float32 / int16 x 2 halves), 8 with follow (likewise).  Any other combination has no kernel: hipErrorInvalidValue.
+template <bool ENC>
+hipError_t launch_half(const PcmLaunch& L, hipStream_t s) {
+  return with_rate(L.rate_hz, [&](auto hz) {
+    return with_sample_type(L.fmt, [&](auto sample) {
+      return with_mode(L.mode, [&](auto upper, auto follow) {
+        constexpr int HZ = decltype(hz)::value;
+        constexpr bool UPPER = decltype(upper)::value, FOLLOW = decltype(follow)::value;
+        using T = decltype(sample);
+        if constexpr (sizeof(T) == 1 ? HZ == 8000 && !UPPER : !UPPER || HZ > 16000) {
+          constexpr int Q = Resample<HZ, ENC>::q;
+          constexpr bool UP = Resample<HZ, ENC>::up;
+          using TI = std::conditional_t<ENC, float, T>;      // the 16 kHz side is float32
+          using TO = std::conditional_t<ENC, T, float>;
+          constexpr int NIN = ENC ? 256 : UP ? 256 / Q : 256 * Q;
+          hipLaunchKernelGGL((pcm_kernel<Q, UP, NIN, TI, TO, UPPER, FOLLOW>), dim3(L.n_hops, L.rows), dim3(kThreads), 0, s, static_cast<const TI*>(L.in),
+                             static_cast<TO*>(L.out), L.taps, L.hist_in, L.hist_out, L.active, L.counts, L.n_hops, L.ub, L.fo);
+          return hipGetLastError();
+        } else {
+          return hipErrorInvalidValue;
+        }
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -506,118 +524,8 @@ std::vector<float> pcm_design(int rate_hz) {
   return out;
 }
 
-hipError_t launch_pcm_decode(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s) {
-  if (fmt == kPcmFmtUlaw || fmt == kPcmFmtAlaw) {      // G.711: 8 kHz alone has the kernels
-    if (rate_hz != 8000) return hipErrorInvalidValue;
-    return fmt == kPcmFmtUlaw ? decode_as<2, true, ulaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
-                              : decode_as<2, true, alaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s);
-  }
-  if (fmt != kPcmFmtF32 && fmt != kPcmFmtS16) return hipErrorInvalidValue;
-#define NUTLS_PCM_DECODE(Q, UP) \
-  return fmt == kPcmFmtS16 ? decode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
-                           : decode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
-  switch (rate_hz) {
-    case 8000: NUTLS_PCM_DECODE(2, true);
-    case 16000: NUTLS_PCM_DECODE(1, false);
-    case 32000: NUTLS_PCM_DECODE(2, false);
-    case 48000: NUTLS_PCM_DECODE(3, false);
-    default: return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_DECODE
-}
-
-hipError_t launch_pcm_encode(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                             const int* counts, int rate_hz, int fmt, int rows, int n_hops, hipStream_t s) {
-  if (fmt == kPcmFmtUlaw || fmt == kPcmFmtAlaw) {
-    if (rate_hz != 8000) return hipErrorInvalidValue;
-    return fmt == kPcmFmtUlaw ? encode_as<2, false, ulaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
-                              : encode_as<2, false, alaw_t>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s);
-  }
-  if (fmt != kPcmFmtF32 && fmt != kPcmFmtS16) return hipErrorInvalidValue;
-#define NUTLS_PCM_ENCODE(Q, UP) \
-  return fmt == kPcmFmtS16 ? encode_as<Q, UP, short>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s) \
-                           : encode_as<Q, UP, float>(in, out, taps, hist_in, hist_out, active, counts, rows, n_hops, s)
-  switch (rate_hz) {
-    case 8000: NUTLS_PCM_ENCODE(2, false);
-    case 16000: NUTLS_PCM_ENCODE(1, false);
-    case 32000: NUTLS_PCM_ENCODE(2, true);
-    case 48000: NUTLS_PCM_ENCODE(3, true);
-    default: return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_ENCODE
-}
-
-hipError_t launch_pcm_decode_upper(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s) {
-  const dim3 grid(n_hops, rows), block(kThreads);
-#define NUTLS_PCM_DECODE_UPPER(Q, T) \
-  hipLaunchKernelGGL((pcm_decode_upper_kernel<Q, T>), grid, block, 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out, active, counts, n_hops, ub)
-  if (rate_hz == 32000) {
-    if (s16) NUTLS_PCM_DECODE_UPPER(2, short);
-    else NUTLS_PCM_DECODE_UPPER(2, float);
-  } else if (rate_hz == 48000) {
-    if (s16) NUTLS_PCM_DECODE_UPPER(3, short);
-    else NUTLS_PCM_DECODE_UPPER(3, float);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_DECODE_UPPER
-  return hipGetLastError();
-}
-
-hipError_t launch_pcm_encode_upper(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                   const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, hipStream_t s) {
-  const dim3 grid(n_hops, rows), block(kThreads);
-#define NUTLS_PCM_ENCODE_UPPER(Q, T) \
-  hipLaunchKernelGGL((pcm_encode_upper_kernel<Q, T>), grid, block, 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out, active, counts, n_hops, ub)
-  if (rate_hz == 32000) {
-    if (s16) NUTLS_PCM_ENCODE_UPPER(2, short);
-    else NUTLS_PCM_ENCODE_UPPER(2, float);
-  } else if (rate_hz == 48000) {
-    if (s16) NUTLS_PCM_ENCODE_UPPER(3, short);
-    else NUTLS_PCM_ENCODE_UPPER(3, float);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_ENCODE_UPPER
-  return hipGetLastError();
-}
-
-hipError_t launch_pcm_decode_follow(const void* in, float* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s) {
-  const dim3 grid(n_hops, rows), block(kThreads);
-#define NUTLS_PCM_DECODE_FOLLOW(Q, T) \
-  hipLaunchKernelGGL((pcm_decode_follow_kernel<Q, T>), grid, block, 0, s, static_cast<const T*>(in), out, taps, hist_in, hist_out, active, counts, n_hops, ub, fo)
-  if (rate_hz == 32000) {
-    if (s16) NUTLS_PCM_DECODE_FOLLOW(2, short);
-    else NUTLS_PCM_DECODE_FOLLOW(2, float);
-  } else if (rate_hz == 48000) {
-    if (s16) NUTLS_PCM_DECODE_FOLLOW(3, short);
-    else NUTLS_PCM_DECODE_FOLLOW(3, float);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_DECODE_FOLLOW
-  return hipGetLastError();
-}
-
-hipError_t launch_pcm_encode_follow(const float* in, void* out, const float* taps, const float* hist_in, float* hist_out, const unsigned char* active,
-                                    const int* counts, int rate_hz, int s16, int rows, int n_hops, const PcmUpper& ub, const PcmFollow& fo, hipStream_t s) {
-  const dim3 grid(n_hops, rows), block(kThreads);
-#define NUTLS_PCM_ENCODE_FOLLOW(Q, T) \
-  hipLaunchKernelGGL((pcm_encode_follow_kernel<Q, T>), grid, block, 0, s, in, static_cast<T*>(out), taps, hist_in, hist_out, active, counts, n_hops, ub, fo)
-  if (rate_hz == 32000) {
-    if (s16) NUTLS_PCM_ENCODE_FOLLOW(2, short);
-    else NUTLS_PCM_ENCODE_FOLLOW(2, float);
-  } else if (rate_hz == 48000) {
-    if (s16) NUTLS_PCM_ENCODE_FOLLOW(3, short);
-    else NUTLS_PCM_ENCODE_FOLLOW(3, float);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef NUTLS_PCM_ENCODE_FOLLOW
-  return hipGetLastError();
+hipError_t launch_pcm(PcmDir dir, const PcmLaunch& L, hipStream_t s) {
+  return dir == PcmDir::kEncode ? launch_half<true>(L, s) : launch_half<false>(L, s);
 }
 
 }  // namespace nutls

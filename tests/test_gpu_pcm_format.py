@@ -114,7 +114,7 @@ def test_halves_against_float64(rate):
 
 
 # ---- 7. int16 is exact ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rate", [8000, 16000, 48000])
+@pytest.mark.parametrize("rate", [8000, 16000, 32000, 48000])
 def test_int16_is_exact(rate):
     hops = 5
     s = as_s16(designed(rate, B, hops, seed=70))
