@@ -487,6 +487,64 @@ int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pc
 int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode);
 int nutls_pcm_decode_block_ragged(nutls_handle* h, const void* pcm_in, float* wave_out, int n_hops, const int* hops, void* stream);
 int nutls_pcm_encode_block_ragged(nutls_handle* h, const float* wave_in, void* pcm_out, int n_hops, const int* hops, void* stream);
+/* Packet mode (streaming handles): the callers' PACKETS in and out, re-framed into hops on the device.  The library's unit of time is the hop,
+ * 16 ms; nothing on the wire arrives in hops -- RTP PCMU / PCMA packets are 20 ms (160 bytes), sometimes 10 or 30, WebRTC's audio processing
+ * runs on 10 ms frames (480 samples at 48 kHz), Opus on 20 ms.  A handle is told ONCE how many samples its callers' packets have
+ * (nutls_set_pcm_packet); nutls_enhance_packet_pcm then takes one packet per stream and returns one packet per stream, and everything between
+ * them -- the per-stream FIFOs in front of the model and behind it, which streams have a whole hop at this tick, the masks that follow, the
+ * second hop of a tick in which a stream has two ready -- happens on the device, with no synchronisation in the device entry.
+ *   Arithmetic (the contract).  S = nutls_pcm_hop_samples, P = the packet's samples at the callers' rate, g = gcd(P, S).  Every stream has an
+ *   input FIFO, which starts empty, and an output FIFO, which starts with D = S - g samples of silence (zeros; in a G.711 format the law's
+ *   silence code, 0xFF / 0xD5).  One call is a TICK.  For every stream whose `active` byte is non-zero it
+ *     1. pushes the stream's P samples onto its input FIFO;
+ *     2. while the input FIFO holds at least S samples: takes the oldest S, runs one hop of the existing pipeline on them -- exactly
+ *        nutls_enhance_hop_pcm_active with a mask of the streams that are ready in this ROUND -- and appends the S results to the output FIFO;
+ *     3. pops P samples from the output FIFO into the stream's row of pcm_out.
+ *   For a stream that is HELD at the tick nothing of it changes -- FIFOs, resampler history, previous hop, overlap tail, model state --, its
+ *   row of pcm_in is not read and its row of pcm_out is silence.
+ *   D is the smallest priming with which step 3 never underruns; after every tick fill_in + fill_out = D, so one counter per stream describes
+ *   both FIFOs; neither ever holds more than S - g + P samples; a tick runs at most R = floor((S - g + P) / S) rounds.
+ *   So the concatenation of a stream's returned packets is D samples of silence followed by the concatenation of what nutls_enhance_hop_pcm
+ *   returns for the stream's concatenated input cut into hops -- bit for bit, whatever the packet length, whichever ticks the stream was
+ *   held at, whenever it joined and whoever shares the handle.  The total delay is D plus the one hop of nutls_enhance_hop plus
+ *   nutls_pcm_delay_samples.
+ *   Buffers: pcm_in / pcm_out are [B, P] of the handle's sample type, rows contiguous, base pointer 16-byte aligned.  `active` as in
+ *   nutls_enhance_hop_pcm_active: DEVICE [B] bytes in nutls_enhance_packet_pcm, HOST memory in the _host entry, NULL = all streams.  The device
+ *   entry is asynchronous on `stream`; the _host entry copies the packets through library buffers and synchronises, like the other _host
+ *   entries of this section.
+ *   Accepted packet lengths: P * bytes per sample is a multiple of 16 (rows stay 16-byte aligned, and every FIFO position is), and
+ *   1 <= P <= 4 S, so R <= 4.  Everything else is NUTLS_ERR_ARG and changes nothing.  nutls_pcm_packet_plan states the rule on the host, with
+ *   no handle and no GPU, as nutls_pcm_filter_taps does: delay = D, rounds = R, fifo = S - g + P (each pointer may be NULL); it knows the
+ *   formats' rules (G.711 at 8000 only; an unknown rate or format is NUTLS_ERR_ARG).
+ *   nutls_set_pcm_packet(h, P), 0 = off (the default), may be called between any two ticks.  Like the other switches of this section it
+ *   synchronises the device; then it re-primes every stream's FIFOs -- input empty, output D samples of silence.  It does not touch the
+ *   resampler histories, the model state or the upper band.  Setting the value in force is a no-op that touches nothing.
+ *   nutls_set_pcm_format turns packet mode OFF, because a new format starts anew and S changes: set the packet length after the format.
+ *   nutls_reset(h, b) re-primes stream b's FIFOs with everything else of the stream, -1 everybody's.  Packet mode changes nothing about the hop
+ *   entries: they neither read nor write the FIFOs.  A packet call while the mode is off is NUTLS_ERR_ARG.
+ *   nutls_pcm_packet_samples = P (0 when off), nutls_pcm_packet_delay_samples = D, nutls_pcm_packet_fill(h, fill, B) = HOST fill[B], the
+ *   samples waiting in each stream's input FIFO, read from the device (synchronises; NUTLS_ERR_ARG while the mode is off or with n other than
+ *   B), nutls_pcm_packet_last_rounds = the hop rounds the last packet call issued.
+ *   Where: streaming handles; an offline handle is refused (its block entries take any number of hops).  When P is not a multiple of S, or when a
+ *   mask is passed, the rounds are masked hops: packet mode is then refused exactly where nutls_step_active refuses a mask, with its reason
+ *   (the baseline variant, NUTLS_CTFA_CAUSAL32, modes 0 / 1) -- checked before anything is pushed, at nutls_set_pcm_packet and again at every
+ *   call, because the mode can change in between: a refused call changes nothing.  With P a multiple of S and no mask it works wherever
+ *   nutls_enhance_hop_pcm does.  Hop fusion, the attenuation limit, the upper band and follow come with the hop entry.
+ *   How many rounds a tick issues: a round nobody is ready for is not free (every held stream costs the state copy of nutls_step_active), so
+ *   the library does not issue one where it can know.  The device keeps the per-stream counters and forms each round's ready mask itself; the
+ *   host keeps a mirror of the same integers for as long as it sees the masks -- active == NULL, or the _host entry -- and issues exactly the
+ *   rounds in which some stream is ready, possibly none; those rounds' masks also feed the bookkeeping behind nutls_state_set that the float
+ *   _host entries do.  With a DEVICE mask the library cannot follow, and from then on every tick issues R rounds (the more expensive
+ *   launches) until nutls_reset(h, -1) or nutls_set_pcm_packet -- the rule of nutls_step_active for masks the host has not seen.
+ *   Cost: a tick of r rounds is r hops of nutls_enhance_hop_pcm_active and r + 1 small launches that move the packets; measured: README, "Packet mode". */
+int nutls_pcm_packet_plan(int rate_hz, int sample_format, int samples, int* delay, int* rounds, int* fifo);  /* host only, no handle */
+int nutls_set_pcm_packet(nutls_handle* h, int samples);      /* 0 = off (the default) */
+int nutls_pcm_packet_samples(nutls_handle* h);               /* P, 0 when off */
+int nutls_pcm_packet_delay_samples(nutls_handle* h);         /* D */
+int nutls_pcm_packet_fill(nutls_handle* h, int* fill, int n);/* HOST [B]: samples waiting in each input FIFO, read from the device; synchronises */
+int nutls_pcm_packet_last_rounds(nutls_handle* h);           /* hop rounds the last packet call issued */
+int nutls_enhance_packet_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream);
+int nutls_enhance_packet_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode);
 
 /* ---- Attenuation limit: a per-row cap on how much noise is removed ------------------------------------------------------
  * Every waveform entry returns the model's full suppression by default.  With a limit l in 0 .. 1 on a row (a stream of a streaming handle,

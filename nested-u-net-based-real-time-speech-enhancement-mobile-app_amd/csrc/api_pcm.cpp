@@ -10,6 +10,7 @@
 // G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8000 Hz only): a format like the others -- nutls_set_pcm_format validates it, sample_bytes is 1, the
 // launch gets the format code; nothing else here knows.  The rule itself is stated once on the host (g711_expand / g711_compress below).
 // The kernel template, its 36 instantiations and the one place that picks among them: pcm.hip.
+#include <algorithm>
 #include <cstdint>
 
 #include "engine.hpp"
@@ -231,14 +232,20 @@ int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops,
 // `samples` of the callers' format to the library's staging, device_path(staged in, staged out) on that stream, the results back, one
 // synchronisation.
 template <typename F>
-int through_staging(Engine* e, const void* pcm_in, void* pcm_out, size_t samples, F device_path) {
+int through_staging(Engine* e, unsigned char* raw_in, unsigned char* raw_out, const void* pcm_in, void* pcm_out, size_t samples, F device_path) {
   const size_t bytes = samples * sample_bytes(e);
-  HIP_TRY(hipMemcpyAsync(e->pcm.raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
-  if (int rc = device_path(e->pcm.raw_in, e->pcm.raw_out)) return rc;
-  HIP_TRY(hipMemcpyAsync(pcm_out, e->pcm.raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(raw_in, pcm_in, bytes, hipMemcpyHostToDevice, e->stream));
+  if (int rc = device_path(raw_in, raw_out)) return rc;
+  HIP_TRY(hipMemcpyAsync(pcm_out, raw_out, bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   enqueue_idle(e);
   return NUTLS_OK;
+}
+
+// ... through the hop and block entries' staging (raw_init)
+template <typename F>
+int through_staging(Engine* e, const void* pcm_in, void* pcm_out, size_t samples, F device_path) {
+  return through_staging(e, e->pcm.raw_in, e->pcm.raw_out, pcm_in, pcm_out, samples, device_path);
 }
 
 // hop_device through the staging (active: HOST mask or null).  The mask is handed on as a device mask: the library does not follow it through
@@ -274,11 +281,144 @@ int aligned16(const void* a, const void* b, const char* who) {
   return NUTLS_OK;
 }
 
+// ---- packet mode (nutls.h, "Packet mode"; the kernels: packet.hip) ------------------------------------------------------------------------------
+int gcd_of(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+// The length rule, host only: what nutls_pcm_packet_plan states and nutls_set_pcm_packet enforces.
+struct PacketPlan {
+  int S, bytes, D, R, L;
+};
+int packet_plan(int rate_hz, int fmt, int samples, PacketPlan* plan, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  if (!pcm_ratio(rate_hz)) return fail(NUTLS_ERR_ARG, w + "rate must be 8000, 16000, 32000 or 48000");
+  if (fmt != NUTLS_PCM_F32 && fmt != NUTLS_PCM_S16 && !g711_format(fmt))
+    return fail(NUTLS_ERR_ARG, w + "sample format must be NUTLS_PCM_F32, NUTLS_PCM_S16, NUTLS_PCM_ULAW or NUTLS_PCM_ALAW");
+  if (g711_format(fmt) && rate_hz != 8000) return fail(NUTLS_ERR_ARG, w + "NUTLS_PCM_ULAW and NUTLS_PCM_ALAW are G.711, which is 8 kHz: rate must be 8000 with them");
+  const int S = NUTLS_FRAME_STEP / 16 * (rate_hz / 1000);
+  const int bytes = g711_format(fmt) ? 1 : fmt == NUTLS_PCM_S16 ? 2 : 4;
+  if (samples < 1 || samples > kPacketMaxRounds * S)
+    return fail(NUTLS_ERR_ARG, w + "a packet has 1 .. " + std::to_string(kPacketMaxRounds * S) + " samples (four hops) at this rate, not " + std::to_string(samples));
+  if (samples * bytes % 16)
+    return fail(NUTLS_ERR_ARG, w + "a packet's bytes must be a multiple of 16 (rows stay 16-byte aligned): " + std::to_string(samples) + " samples of " +
+                                   std::to_string(bytes) + " bytes are not");
+  const int g = gcd_of(samples, S);
+  *plan = {S, bytes, S - g, (S - g + samples) / S, S - g + samples};
+  return NUTLS_OK;
+}
+
+// Two device buffers of one size that grow with the largest request a handle has seen (the old ones are freed: nothing is queued on them, the
+// callers have synchronised).
+int grow_pair(Engine* e, size_t bytes, unsigned char** a, unsigned char** b, size_t* cap) {
+  if (*cap >= bytes) return NUTLS_OK;
+  for (unsigned char** p : {a, b}) {
+    if (*p) {
+      e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), static_cast<void*>(*p)));
+      HIP_TRY(hipFree(*p));
+      *p = nullptr;
+    }
+    if (int rc = dev_alloc_once(e, bytes, p, true)) return rc;
+  }
+  *cap = bytes;
+  return NUTLS_OK;
+}
+
+// Row idx's (< 0: every row's) FIFOs as a stream starts with them: input empty, output D samples of silence (the whole ring row is filled with
+// the silence byte, of which the first D samples count).  The mirror follows where the host still has one.
+int packet_prime(Engine* e, int idx) {
+  PacketState& k = e->pkt;
+  if (!k.P) return NUTLS_OK;
+  const size_t row = static_cast<size_t>(k.L) * k.bytes, first = idx < 0 ? 0 : static_cast<size_t>(idx), n = idx < 0 ? static_cast<size_t>(e->B) : 1;
+  HIP_TRY(hipMemset(k.ctr + first, 0, n * sizeof(PacketCtr)));
+  HIP_TRY(hipMemset(k.out_ring + first * row, static_cast<int>(k.silence & 0xFF), n * row));
+  if (idx < 0) {
+    k.mirror.assign(static_cast<size_t>(e->B), 0);
+    k.mirror_known = true;
+  } else if (k.mirror_known) {
+    k.mirror[first] = 0;
+  }
+  return NUTLS_OK;
+}
+
+// A tick's rounds need masked hops when the packets do not cut into whole hops or when the caller passes a mask: then packet mode works where
+// check_active says masks do, and says so with its reason.
+bool packet_masked(int samples, int S, const unsigned char* active) { return samples % S != 0 || active != nullptr; }
+
+// what both packet entries check before anything is pushed: a refused call changes nothing
+int packet_refusals(nutls_handle* h, bool pointers_ok, const unsigned char* active, int dc_mode, const char* who) {
+  if (int rc = hop_args(h, pointers_ok, who)) return rc;
+  const Engine* e = &h->eng;
+  if (!e->pkt.P) return fail(NUTLS_ERR_ARG, std::string(who) + ": packet mode is off (nutls_set_pcm_packet with the packets' samples first)");
+  if (int rc = dc_ok(dc_mode, who)) return rc;
+  if (packet_masked(e->pkt.P, e->pkt.S, active)) return check_active(e, who);
+  return e->mode == 3 ? NUTLS_OK : refuse_per_layer_in_causal32(e, who);
+}
+
+// One hop round on the library's hop buffers: the existing hop entry of the handle's format (ready: DEVICE mask or null)
+int packet_hop(nutls_handle* h, const void* in, void* out, const unsigned char* ready, int dc_mode, hipStream_t s) {
+  if (plain_format(&h->eng)) return nutls_enhance_hop_active(h, static_cast<const float*>(in), static_cast<float*>(out), ready, dc_mode, s);
+  return hop_device(h, in, out, ready, dc_mode, s);
+}
+
+// One tick on stream s (the handle's device is current, every refusal is behind us).  active: the DEVICE mask the kernels read, or null;
+// seen: the same mask in HOST memory where the host has it (the _host entry), null otherwise.  How many rounds: while the host has a mirror of
+// the counters, exactly those in which some stream is ready -- each round's ready mask goes to note_active, as the float _host entries' masks
+// do --; after a DEVICE mask the mirror is unknown and every tick issues R rounds, whose ready masks only the device knows.
+int packet_tick(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, const unsigned char* seen, int dc_mode, hipStream_t s) {
+  Engine* e = &h->eng;
+  PacketState& k = e->pkt;
+  const bool masked = packet_masked(k.P, k.S, active);
+  if (active && !seen) k.mirror_known = false;
+  std::vector<std::vector<unsigned char>> ready;      // per round, while the mirror is known
+  int rounds = k.R;
+  if (k.mirror_known) {
+    for (int b = 0; b < e->B; ++b)
+      if (!seen || seen[b]) k.mirror[b] += k.P;
+    for (;;) {
+      std::vector<unsigned char> m(static_cast<size_t>(e->B), 0);
+      bool any = false;
+      for (int b = 0; b < e->B; ++b)
+        if ((!seen || seen[b]) && k.mirror[b] >= k.S) {
+          k.mirror[b] -= k.S;
+          m[b] = 1;
+          any = true;
+        }
+      if (!any) break;
+      ready.push_back(std::move(m));
+    }
+    rounds = static_cast<int>(ready.size());
+  }
+  if (int rc = enqueue_on(e, s)) return rc;
+  const int q = 16 / k.bytes;      // samples of a quad
+  const PacketLaunch L = {pcm_in, pcm_out, active, k.in_ring, k.out_ring, k.hop_in, k.hop_out, k.ctr, k.ready, e->B, k.P / q, k.S / q, k.D / q, k.L / q, k.silence};
+  k.last_rounds = rounds;
+  if (rounds == 0) {
+    HIP_TRY(launch_packet(PacketBody::kPushPop, L, s));
+    return NUTLS_OK;
+  }
+  HIP_TRY(launch_packet(PacketBody::kPushStage, L, s));
+  for (int r = 0; r < rounds; ++r) {
+    if (int rc = packet_hop(h, k.hop_in, k.hop_out, masked ? k.ready : nullptr, dc_mode, s)) return rc;
+    if (masked && k.mirror_known) note_active(e, ready[r].data());
+    HIP_TRY(launch_packet(r + 1 < rounds ? PacketBody::kTurn : PacketBody::kTurnPop, L, s));
+  }
+  return NUTLS_OK;
+}
+
 }  // namespace
 
 namespace nutls {
 
-int pcm_reset(Engine* e, int idx) { return zero_histories(e, idx); }
+int pcm_reset(Engine* e, int idx) {
+  if (int rc = zero_histories(e, idx)) return rc;
+  return packet_prime(e, idx);
+}
 
 }  // namespace nutls
 
@@ -331,6 +471,7 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
     e->pcm.fmt = sample_format;
     e->pcm.upper = 0.f;
     e->pcm.follow = false;
+    e->pkt.P = 0;      // (packet mode is off again: below)
     return NUTLS_OK;
   }
   HIP_TRY(hipSetDevice(e->device));
@@ -339,6 +480,7 @@ int nutls_set_pcm_format(nutls_handle* h, int rate_hz, int sample_format) {
   e->pcm.fmt = sample_format;
   e->pcm.upper = 0.f;                   // a new format starts anew: the upper band is off until nutls_set_pcm_upper_band
   e->pcm.follow = false;                // ... and with it follow
+  e->pkt.P = 0;                         // ... and packet mode: S changes with the rate (nutls_set_pcm_packet after the format)
   if (!e->pcm.ready) {
     if (int rc = pcm_init(e)) return rc;      // (uploads the taps, zeroes the histories)
   } else {
@@ -460,6 +602,105 @@ int nutls_pcm_decode_hop(nutls_handle* h, const void* pcm_in, float* hop_out, co
 int nutls_pcm_encode_hop(nutls_handle* h, const float* hop_in, void* pcm_out, const unsigned char* active, void* stream) {
   if (int rc = hop_args(h, hop_in && pcm_out, "nutls_pcm_encode_hop")) return rc;
   return half_entry(h, PcmDir::kEncode, hop_in, pcm_out, active, 1, stream);
+}
+
+// ---- streaming handles, packet mode: the callers' packets re-framed into hops on the device -----------------------------------------------------
+int nutls_pcm_packet_plan(int rate_hz, int sample_format, int samples, int* delay, int* rounds, int* fifo) {
+  PacketPlan p;
+  if (int rc = packet_plan(rate_hz, sample_format, samples, &p, "nutls_pcm_packet_plan")) return rc;
+  if (delay) *delay = p.D;
+  if (rounds) *rounds = p.R;
+  if (fifo) *fifo = p.L;
+  return NUTLS_OK;
+}
+
+int nutls_set_pcm_packet(nutls_handle* h, int samples) {
+  const char* who = "nutls_set_pcm_packet";
+  if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null handle");
+  Engine* e = &h->eng;
+  PacketState& k = e->pkt;
+  if (samples == k.P) return NUTLS_OK;      // nothing is touched
+  if (e->offline)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": offline handle (nutls_create_offline): packets are a streaming handle's -- nutls_enhance_block_pcm takes any number of hops");
+  PacketPlan p = {};
+  if (samples != 0) {
+    if (int rc = packet_plan(e->pcm.rate, e->pcm.fmt, samples, &p, who)) return rc;
+    if (packet_masked(samples, p.S, nullptr))
+      if (int rc = check_active(e, who)) return rc;      // (packets that do not cut into whole hops: every tick's rounds are masked hops)
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // queued ticks still read the rings and counters that change below
+  if (samples == 0) {
+    k.P = 0;
+    return NUTLS_OK;
+  }
+  if (!plain_format(e))
+    if (int rc = pcm_init(e)) return rc;
+  const size_t rows = static_cast<size_t>(e->B);
+  int rc;
+  if ((rc = grow_pair(e, rows * p.L * p.bytes, &k.in_ring, &k.out_ring, &k.ring_cap)) || (rc = grow_pair(e, rows * p.S * p.bytes, &k.hop_in, &k.hop_out, &k.hop_cap)) ||
+      (rc = dev_alloc_once(e, rows, &k.ctr, true)) || (rc = dev_alloc_once(e, rows, &k.ready, true)))
+    return rc;
+  k.P = samples;
+  k.S = p.S;
+  k.D = p.D;
+  k.R = p.R;
+  k.L = p.L;
+  k.bytes = p.bytes;
+  k.silence = e->pcm.fmt == NUTLS_PCM_ULAW ? 0xFFFFFFFFu : e->pcm.fmt == NUTLS_PCM_ALAW ? 0xD5D5D5D5u : 0u;
+  k.last_rounds = 0;
+  if ((rc = packet_prime(e, -1))) return rc;      // every stream: input empty, output D samples of silence; the mirror is known again
+  HIP_TRY(hipDeviceSynchronize());
+  return NUTLS_OK;
+}
+
+int nutls_pcm_packet_samples(nutls_handle* h) { return h ? h->eng.pkt.P : fail(NUTLS_ERR_ARG, "nutls_pcm_packet_samples: null handle"); }
+
+int nutls_pcm_packet_delay_samples(nutls_handle* h) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_pcm_packet_delay_samples: null handle");
+  return h->eng.pkt.P ? h->eng.pkt.D : 0;
+}
+
+int nutls_pcm_packet_last_rounds(nutls_handle* h) {
+  if (!h) return fail(NUTLS_ERR_ARG, "nutls_pcm_packet_last_rounds: null handle");
+  return h->eng.pkt.P ? h->eng.pkt.last_rounds : 0;
+}
+
+int nutls_pcm_packet_fill(nutls_handle* h, int* fill, int n) {
+  if (!h || !fill) return fail(NUTLS_ERR_ARG, "nutls_pcm_packet_fill: null pointer");
+  Engine* e = &h->eng;
+  const PacketState& k = e->pkt;
+  if (!k.P) return fail(NUTLS_ERR_ARG, "nutls_pcm_packet_fill: packet mode is off (nutls_set_pcm_packet)");
+  if (n != e->B) return fail(NUTLS_ERR_ARG, "nutls_pcm_packet_fill: n must be the handle's streams, " + std::to_string(e->B));
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // the ticks queued on the callers' streams have written what is read here
+  HIP_TRY(hipMemcpy2D(fill, sizeof(int), &k.ctr[0].fill, sizeof(PacketCtr), sizeof(int), static_cast<size_t>(n), hipMemcpyDeviceToHost));
+  for (int b = 0; b < n; ++b) fill[b] *= 16 / k.bytes;      // quads -> samples
+  return NUTLS_OK;
+}
+
+int nutls_enhance_packet_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  if (int rc = packet_refusals(h, pcm_in && pcm_out, active, dc_mode, "nutls_enhance_packet_pcm")) return rc;
+  HIP_TRY(hipSetDevice(h->eng.device));
+  return packet_tick(h, pcm_in, pcm_out, active, nullptr, dc_mode, static_cast<hipStream_t>(stream));
+}
+
+// the tick through the staging (active: HOST mask or null): the host sees the mask, so the mirror of the counters stays known
+int nutls_enhance_packet_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode) {
+  if (int rc = packet_refusals(h, pcm_in && pcm_out, active, dc_mode, "nutls_enhance_packet_pcm_host")) return rc;
+  Engine* e = &h->eng;
+  PacketState& k = e->pkt;
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = grow_pair(e, static_cast<size_t>(e->B) * k.P * k.bytes, &k.raw_in, &k.raw_out, &k.raw_cap)) return rc;
+  if (int rc = enqueue_on(e, e->stream)) return rc;      // (behind what earlier calls queued on the callers' streams)
+  const unsigned char* d_act = nullptr;
+  if (active) {
+    if (int rc = dev_alloc_once(e, static_cast<size_t>(e->B), &e->pcm.d_active, false)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->pcm.d_active, active, static_cast<size_t>(e->B), hipMemcpyHostToDevice, e->stream));
+    d_act = e->pcm.d_active;
+  }
+  return through_staging(e, k.raw_in, k.raw_out, pcm_in, pcm_out, static_cast<size_t>(e->B) * k.P,
+                         [&](const void* in, void* out) { return packet_tick(h, in, out, d_act, active, dc_mode, e->stream); });
 }
 
 // ---- offline handles --------------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,20 @@
 
 using namespace nutls;
 
+// After a masked step whose mask the host has seen (the _host entries; the rounds of a packet call, api_pcm.cpp): the streams that took the
+// frame have replaced every row nutls_state_set gave them; once all have, masked launches go back to leaving the lazily written states to
+// states_materialize.  (A device mask is not visible here: with those, eager launches last until a step of all streams -- nutls.h,
+// nutls_step_active.)
+void nutls::note_active(Engine* e, const unsigned char* active) {
+  if (!e->lazy_edited) return;
+  bool pending = false;
+  for (int b = 0; b < e->B; ++b) {
+    if (active[b]) e->lazy_pending[b] = 0;
+    pending = pending || e->lazy_pending[b];
+  }
+  if (!pending) e->lazy_edited = false;
+}
+
 extern "C" {
 
 // ---- page-locked host buffers (nutls_host_alloc): base -> bytes ---------------------------------------------------------
@@ -85,19 +99,6 @@ static int upload_active(Engine* e, const unsigned char* active) {
   if (int rc = dev_alloc_once(e, static_cast<size_t>(e->B), &e->d_active, false)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_active, active, static_cast<size_t>(e->B), hipMemcpyHostToDevice, e->stream));
   return NUTLS_OK;
-}
-
-// After a masked step whose mask the host has seen (the _host entries): the streams that took the frame have replaced every row
-// nutls_state_set gave them; once all have, masked launches go back to leaving the lazily written states to states_materialize.
-// (A device mask is not visible here: with those, eager launches last until a step of all streams -- nutls.h, nutls_step_active.)
-static void note_active(Engine* e, const unsigned char* active) {
-  if (!e->lazy_edited) return;
-  bool pending = false;
-  for (int b = 0; b < e->B; ++b) {
-    if (active[b]) e->lazy_pending[b] = 0;
-    pending = pending || e->lazy_pending[b];
-  }
-  if (!pending) e->lazy_edited = false;
 }
 
 // (active non-null: checked by the caller, fused mode)

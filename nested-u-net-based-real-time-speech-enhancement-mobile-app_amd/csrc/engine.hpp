@@ -15,6 +15,7 @@
 #include "fused_host.hpp"
 #include "ragged.hpp"
 #include "pcm.hpp"
+#include "packet.hpp"
 
 namespace nutls {
 
@@ -203,6 +204,7 @@ struct Engine {
   bool atten_on = false;
   // ---- PCM gateway ---------------------------------------------------------------------------
   PcmState pcm;          // the callers' sample rate and type (nutls_set_pcm_format) and the resampler histories of the _pcm entries
+  PacketState pkt;       // packet mode (nutls_set_pcm_packet): the callers' packet length, the per-stream FIFOs and their counters
 
   ~Engine() {
     for (int i = 0; i < 2; ++i)
@@ -261,8 +263,13 @@ int build_offline_plan(Engine* e);
 // to e->d_counts on the library's stream, in front of the work that reads them.
 int upload_counts(Engine* e, const int* counts, int n, const char* who);
 
+// ---- api_stream.cpp --------------------------------------------------------------------------
+// After a masked step whose HOST mask `active` [B] the library has seen: the lazy_pending bookkeeping behind nutls_state_set (see there)
+void note_active(Engine* e, const unsigned char* active);
+
 // ---- api_pcm.cpp -----------------------------------------------------------------------------
-// nutls_reset: zero the resampler histories and the upper-band state of row `idx` (stream / utterance; < 0: every row's) where they exist
+// nutls_reset: zero the resampler histories and the upper-band state of row `idx` (stream / utterance; < 0: every row's) where they exist,
+// and re-prime the row's packet FIFOs while packet mode is on
 int pcm_reset(Engine* e, int idx);
 
 }  // namespace nutls

@@ -59,6 +59,8 @@ ABI_SYMBOLS = (
     "nutls_set_pcm_upper_band", "nutls_pcm_upper_band",
     "nutls_set_pcm_upper_follow", "nutls_pcm_upper_follow", "nutls_pcm_follow_gain",
     "nutls_set_atten_limit", "nutls_atten_limit", "nutls_istft_block_mix",
+    "nutls_pcm_packet_plan", "nutls_set_pcm_packet", "nutls_pcm_packet_samples", "nutls_pcm_packet_delay_samples", "nutls_pcm_packet_fill",
+    "nutls_pcm_packet_last_rounds", "nutls_enhance_packet_pcm", "nutls_enhance_packet_pcm_host",
 )
 # ... and the declared symbols whose names carry a digit, listed apart: tests/test_abi.py compares ABI_SYMBOLS with the names it finds in
 # the header by a pattern of lower-case letters and underscores, which cannot see these
@@ -177,6 +179,16 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_set_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
         lib.nutls_atten_limit.argtypes = [c.c_void_p, fp, c.c_int]
         lib.nutls_istft_block_mix.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_int, c.c_void_p]
+    if not dev_lib or hasattr(lib, "nutls_set_pcm_packet"):
+        vp, ip = c.c_void_p, c.POINTER(c.c_int)
+        lib.nutls_pcm_packet_plan.argtypes = [c.c_int, c.c_int, c.c_int, ip, ip, ip]
+        lib.nutls_set_pcm_packet.argtypes = [vp, c.c_int]
+        lib.nutls_pcm_packet_samples.argtypes = [vp]
+        lib.nutls_pcm_packet_delay_samples.argtypes = [vp]
+        lib.nutls_pcm_packet_fill.argtypes = [vp, ip, c.c_int]
+        lib.nutls_pcm_packet_last_rounds.argtypes = [vp]
+        lib.nutls_enhance_packet_pcm.argtypes = [vp, vp, vp, vp, c.c_int, vp]
+        lib.nutls_enhance_packet_pcm_host.argtypes = [vp, vp, vp, vp, c.c_int]
     if not dev_lib or hasattr(lib, "nutls_pcm_g711_expand"):
         lib.nutls_pcm_g711_expand.argtypes = [c.c_int, c.POINTER(c.c_short), c.c_int]
         lib.nutls_pcm_g711_compress.argtypes = [c.c_int, c.POINTER(c.c_short), c.POINTER(c.c_ubyte), c.c_size_t]
@@ -252,6 +264,20 @@ def pcm_filter(rate: int, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
     taps = np.empty(n, np.float32)
     _check(lib, lib.nutls_pcm_filter(int(rate), _fptr(taps), n))
     return taps
+
+
+def pcm_packet_plan(rate: int, dtype, samples: int, lib: Optional[ctypes.CDLL] = None) -> dict:
+    """What packet mode makes of packets of ``samples`` samples at ``rate`` in ``dtype`` ("float32", "int16", "ulaw", "alaw"):
+    ``{"delay": D, "rounds": R, "fifo": S - g + P}`` -- the silence in front of every stream, the hop rounds a tick can take and the samples
+    each FIFO can hold (``nutls_pcm_packet_plan``).  Host only: needs no GPU.  ``ValueError``: a rate, format or length that is not accepted
+    (the packet's bytes a multiple of 16, 1 .. 4 hops)."""
+    name = dtype if isinstance(dtype, str) and dtype in G711_CODECS else np.dtype(dtype).name
+    if name not in _PcmFormat._PCM_FORMATS:
+        raise ValueError("dtype must be float32, int16, 'ulaw' or 'alaw', got %s" % name)
+    lib = lib or load_library()
+    d, r, f = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib, lib.nutls_pcm_packet_plan(int(rate), _PcmFormat._PCM_FORMATS[name], int(samples), ctypes.byref(d), ctypes.byref(r), ctypes.byref(f)))
+    return {"delay": d.value, "rounds": r.value, "fifo": f.value}
 
 
 # G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW; 8000 Hz only): the codec names, their format codes and the silence code of each -- what a zero
@@ -715,6 +741,73 @@ class NutlsEngine(_PcmFormat):
         o = torch.empty((self.batch, S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None else self._pcm_tensor(out, self.batch, S, "out")
         a = None if active is None else self._device_mask(active, x)
         _check(self._lib, self._lib.nutls_pcm_encode_hop(self._h, x.data_ptr(), o.data_ptr(), a, torch.cuda.current_stream(x.device).cuda_stream))
+        return o
+
+    # -- packet mode: the callers' 10 / 20 ms packets re-framed into hops on the device (csrc/packet.hip) -------------------------
+    def set_pcm_packet(self, samples=None, ms=None) -> None:
+        """The callers' packet length for ``enhance_packet_pcm``: ``samples`` at the callers' rate, or ``ms`` milliseconds (``ms=20`` ->
+        ``pcm_rate * 20 / 1000``, which must be a whole number); ``samples=0``, or neither, turns packet mode off
+        (``nutls_set_pcm_packet``).  May be called between any two ticks: every stream's FIFOs start anew -- input empty, output
+        ``pcm_packet_delay_samples`` samples of silence --, model state and resampler histories stay (nothing happens when the length is
+        the one in force).  ``set_pcm_format`` turns packet mode off, so call this after it.  ``ValueError``: a length whose bytes are no
+        multiple of 16 or that is outside 1 .. 4 hops, or a handle that cannot hold streams (see ``step``'s ``active``) with a length
+        that is no multiple of the hop -- nothing changes."""
+        if samples is not None and ms is not None:
+            raise ValueError("give samples or ms, not both")
+        if ms is not None:
+            n = self.pcm_rate * ms / 1000.0
+            if n != int(n):
+                raise ValueError("%r ms are not a whole number of samples at %d Hz" % (ms, self.pcm_rate))
+            samples = int(n)
+        _check(self._lib, self._lib.nutls_set_pcm_packet(self._h, int(samples or 0)))
+
+    @property
+    def pcm_packet_samples(self) -> int:
+        """Samples of a packet (``nutls_pcm_packet_samples``); 0: packet mode is off."""
+        return int(self._lib.nutls_pcm_packet_samples(self._h))
+
+    @property
+    def pcm_packet_delay_samples(self) -> int:
+        """``D = S - gcd(P, S)``: the samples of silence in front of every stream's packets; ``pcm_delay_samples`` and the one hop of
+        ``enhance_hop`` come on top (``nutls_pcm_packet_delay_samples``)."""
+        return int(self._lib.nutls_pcm_packet_delay_samples(self._h))
+
+    @property
+    def pcm_packet_last_rounds(self) -> int:
+        """Hop rounds the last ``enhance_packet_pcm`` call issued (``nutls_pcm_packet_last_rounds``)."""
+        return int(self._lib.nutls_pcm_packet_last_rounds(self._h))
+
+    def pcm_packet_fill(self) -> np.ndarray:
+        """``[B]`` int32: the samples waiting in each stream's input FIFO, read from the device (``nutls_pcm_packet_fill``; synchronises).
+        ``ValueError`` while packet mode is off."""
+        f = np.zeros(self.batch, np.int32)
+        _check(self._lib, self._lib.nutls_pcm_packet_fill(self._h, f.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(f)))
+        return f
+
+    def enhance_packet_pcm(self, pcm, dc_mode: str = "edge", out=None, active=None):
+        """One packet of every stream in, one packet out (``set_pcm_packet``): ``pcm [B, pcm_packet_samples]`` of the handle's sample type
+        (``uint8`` in a G.711 format), a CUDA tensor (``nutls_enhance_packet_pcm``, asynchronous on the current torch stream) or a numpy
+        array (``nutls_enhance_packet_pcm_host``, synchronous).  The concatenated packets of a stream are ``pcm_packet_delay_samples`` of
+        silence, then what ``enhance_hop_pcm`` returns for the stream's concatenated input cut into hops, bit for bit.  ``active``: as in
+        ``enhance_hop_pcm`` -- a held stream's FIFOs stay as they are too, its packet of the output is silence."""
+        if dc_mode not in self._DC:
+            raise ValueError("dc_mode must be 'edge' or 'zero'")
+        P = self.pcm_packet_samples
+        if P == 0:
+            raise ValueError("packet mode is off (set_pcm_packet)")
+        if isinstance(pcm, np.ndarray):
+            x = self._pcm_array(pcm, self.batch, P, "pcm")
+            o = np.empty_like(x) if out is None else self._pcm_array(out, self.batch, P, "out")
+            a = None if active is None else self._host_mask(active)
+            _check(self._lib, self._lib.nutls_enhance_packet_pcm_host(self._h, x.ctypes.data, o.ctypes.data, None if a is None else a.ctypes.data,
+                                                                      self._DC[dc_mode]))
+            return o
+        import torch
+        x = self._pcm_tensor(pcm, self.batch, P, "pcm")
+        o = torch.empty_like(x) if out is None else self._pcm_tensor(out, self.batch, P, "out")
+        a = None if active is None else self._device_mask(active, x)
+        _check(self._lib, self._lib.nutls_enhance_packet_pcm(self._h, x.data_ptr(), o.data_ptr(), a, self._DC[dc_mode],
+                                                            torch.cuda.current_stream(x.device).cuda_stream))
         return o
 
     def step_resident(self, stream: int = 0):
