@@ -111,27 +111,21 @@ static int stft_block_launch(Engine* e, const float* pcm_in, float* mag, int n_h
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
   if (int rc = enqueue_on(e, s)) return rc;
-  if (hops) HIP_TRY(launch_stft_block_ragged(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, hops, e->outt, n_hops, s));
-  else HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, e->outt, n_hops, s));
+  HIP_TRY(launch_stft_block(pcm_in, e->fb_tail[e->fb_tail_par], e->fb_tail[1 - e->fb_tail_par], e->fb_win, e->fb_tw, mag, e->fb_ph, hops, e->outt, n_hops, s));
   e->fb_tail_par ^= 1;
   e->fb_hops = n_hops;
   return NUTLS_OK;
 }
 
 // noisy: the magnitudes of the same block (the enhance entries: io_in; nutls_istft_block_mix: the caller's) or null (the stand-alone half, which
-// has none).  With noisy rows and an attenuation limit in force (nutls_set_atten_limit) the mix kernel runs for the whole launch.
+// has none).  With noisy rows and an attenuation limit in force (nutls_set_atten_limit) the mix runs for the whole launch.
 static int istft_block_launch(Engine* e, const float* mag, const float* noisy, float* pcm_out, int n_hops, int dc_mode, hipStream_t s, const int* hops = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
   if (int rc = frontend_block_init(e)) return rc;
   if (n_hops != e->fb_hops) return fail(NUTLS_ERR_ARG, "nutls_istft_block: n_hops differs from the block the phasors inside the handle belong to (nutls_stft_block first)");
   if (int rc = enqueue_on(e, s)) return rc;
-  if (noisy && e->atten_on)
-    HIP_TRY(launch_istft_block_mix(mag, noisy, e->d_atten, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
-                                   dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
-  else if (hops) HIP_TRY(launch_istft_block_ragged(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
-                                              dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
-  else HIP_TRY(launch_istft_block(mag, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par], e->fb_ola[1 - e->fb_ola_par], pcm_out,
-                                  dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->outt, n_hops, s));
+  HIP_TRY(launch_istft_block(mag, e->atten_on ? noisy : nullptr, e->d_atten, e->fb_ph, e->fb_inv, e->fb_tw, e->fb_ola[e->fb_ola_par],
+                             e->fb_ola[1 - e->fb_ola_par], pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, hops, e->outt, n_hops, s));
   e->fb_ola_par ^= 1;
   return NUTLS_OK;
 }

@@ -207,14 +207,11 @@ static int istft_hop_impl(nutls_handle* h, float* pcm_out, int dc_mode, const un
   int rc = frontend_init(e);
   if (rc) return rc;
   if ((rc = enqueue_on(e, static_cast<hipStream_t>(stream)))) return rc;
-  // an attenuation limit in force (nutls_set_atten_limit): the mix kernel for the whole launch, the noisy rows being io_in as the analysis left them
+  // an attenuation limit in force (nutls_set_atten_limit): the mix for the whole launch, the noisy rows being io_in as the analysis left them
   // (an offline handle's limits are per utterance, not per arena slot: they belong to its block entries)
-  if (e->atten_on && !e->offline)
-    HIP_TRY(launch_istft_hop_mix(e->io_out, e->io_in, e->d_atten, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0,
-                                 e->B, static_cast<hipStream_t>(stream), active));
-  else
-    HIP_TRY(launch_istft_hop(e->io_out, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->B,
-                             static_cast<hipStream_t>(stream), active));
+  const float* noisy = e->atten_on && !e->offline ? e->io_in : nullptr;
+  HIP_TRY(launch_istft_hop(e->io_out, noisy, e->d_atten, e->fe_ph, e->fe_inv, e->fe_tw, e->fe_ola, pcm_out, dc_mode == NUTLS_DC_EDGE ? 1 : 0, e->B,
+                           static_cast<hipStream_t>(stream), active));
   return NUTLS_OK;
 }
 

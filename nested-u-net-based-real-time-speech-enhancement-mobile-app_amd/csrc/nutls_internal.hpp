@@ -216,24 +216,23 @@ constexpr int NUTLS_FRAME_STEP = 256;   // interpreter_proposed.py:18
 // previous hop / the overlap tail untouched; the analysis writes nothing for it, the synthesis a zero hop.
 hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, const float* tw, float* mag, float* ph, int B, hipStream_t s,
                            const unsigned char* active = nullptr);
-hipError_t launch_istft_hop(const float* est, const float* ph, const float* inv_win, const float* tw, float* ola, float* pcm_out,
-                            int dc_edge, int B, hipStream_t s, const unsigned char* active = nullptr);
+// Both syntheses, noisy non-null: with an attenuation limit (nutls_set_atten_limit).  noisy = the magnitudes of the same frames ([B][256] /
+// [U][n_hops][256]), lim = one (l, c) float pair per stream / utterance, c = 1 - l formed on the host; each bin is synthesised from
+// fma(l, noisy, c * est).  noisy null: the estimates as they are, lim is not read.
+hipError_t launch_istft_hop(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                            float* ola, float* pcm_out, int dc_edge, int B, hipStream_t s, const unsigned char* active = nullptr);
 // Waveform block mode of the offline handles (stft_block.hip): the same analysis / synthesis for n_hops consecutive hops of each of U
 // utterances in one launch.  pcm / pcm_out [U][n_hops * 256]; mag / est [U][n_hops][256]; ph [U][n_hops][257] float2.  The carried previous hop
 // (tail) and overlap tail (ola), [U][256], are read from *_in and written to *_out: two buffers each, since the first tile of an utterance reads
 // what its last tile replaces.  win / inv_win as above; tw = stft_block_twiddles() on the device.
+// hops non-null: ragged blocks (nutls_process_block_ragged, nutls_enhance_block_ragged), a DEVICE array [U] of per-utterance hop counts, clamped
+// to 0 .. n_hops.  Hops behind hops[u] are not read, their magnitudes / PCM rows are written with zeros, and the carried hop / overlap tail is
+// taken behind hop hops[u] - 1 (copied across from the input buffer where hops[u] = 0).  hops null: every utterance has n_hops hops.
 std::vector<float> stft_block_twiddles();
 hipError_t launch_stft_block(const float* pcm, const float* tail_in, float* tail_out, const float* win, const float* tw, float* mag, float* ph,
-                             int U, int n_hops, hipStream_t s);
-hipError_t launch_istft_block(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
-                              float* pcm_out, int dc_edge, int U, int n_hops, hipStream_t s);
-// The two syntheses with an attenuation limit (nutls_set_atten_limit): noisy = the magnitudes of the same frames ([B][256] / [U][n_hops][256]),
-// lim = one (l, c) float pair per stream / utterance, c = 1 - l formed on the host; each bin is synthesised from fma(l, noisy, c * est).
-// hops: DEVICE per-utterance counts as in launch_istft_block_ragged, or null for the uniform block.
-hipError_t launch_istft_hop_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
-                                float* ola, float* pcm_out, int dc_edge, int B, hipStream_t s, const unsigned char* active = nullptr);
-hipError_t launch_istft_block_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
-                                  const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s);
+                             const int* hops, int U, int n_hops, hipStream_t s);
+hipError_t launch_istft_block(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                              const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s);
 // (Rounds 1-3 kept a third kernel family here: a persistent plan-interpreter kernel, megakernel.hip, execution mode 2 -- retired in
 //  round 4: the fused kernel is the one-launch path, the per-layer kernels below are the cross-check and the block mode.)
 

@@ -1,6 +1,6 @@
 // Ragged blocks of the offline batch handles (nutls_process_block_ragged, nutls_enhance_block_ragged): launchers of the stage-in /
-// commit kernels (ragged.hip) and of the count-aware block transforms (stft_block.hip).  Kept apart from nutls_internal.hpp: the
-// frame-step kernels include that header and have nothing to do with these.
+// commit kernels (ragged.hip).  Kept apart from nutls_internal.hpp: the frame-step kernels include that header and have nothing to
+// do with these.  (The block transforms take the same counts as an optional argument: launch_stft_block / launch_istft_block there.)
 //
 // `counts` is a DEVICE array [U] of int, read by the kernels: utterance u has counts[u] real leading frames in a block whose row
 // stride is n (every kernel clamps it to 0 .. n).
@@ -19,13 +19,5 @@ hipError_t launch_ragged_state_gather(float* arena, long long slot_floats, int s
 // Time-attention history [U][12 stages][rows_per_stage][64] of the causal32 CTFA: rows counts[u] .. counts[u] + 30 of every stage
 // become rows 0 .. 30 (in place; correct for counts below 31, where the two ranges overlap).
 hipError_t launch_ragged_hist_roll(float* hist, int rows_per_stage, const int* counts, int U, int n, hipStream_t s);
-
-// launch_stft_block / launch_istft_block (nutls_internal.hpp) with per-utterance hop counts: hops behind hops[u] are not read, their
-// magnitudes / PCM rows are written with zeros, and the carried hop / overlap tail is taken behind hop hops[u] - 1 (copied across
-// from the input buffer where hops[u] = 0).
-hipError_t launch_stft_block_ragged(const float* pcm, const float* tail_in, float* tail_out, const float* win, const float* tw, float* mag, float* ph,
-                                    const int* hops, int U, int n_hops, hipStream_t s);
-hipError_t launch_istft_block_ragged(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
-                                     float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s);
 
 }  // namespace nutls

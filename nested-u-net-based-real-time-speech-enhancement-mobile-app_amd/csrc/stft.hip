@@ -71,10 +71,16 @@ __global__ __launch_bounds__(256) void stft_hop_kernel(const float* __restrict__
 
 // est [B,256] model output (bins 1..256); ph phasors of the same frame; ola [B,256] overlap tail (updated);
 // pcm_out [B,256].  dc_edge: bin 0 = est[0] (PC loop) else 0 (phone).
+// MIX, the attenuation limit (nutls_set_atten_limit): noisy [B,256] the magnitudes of the same frame as stft_hop_kernel left them, lim [B] =
+// (l, c) with c = 1 - l formed on the host.  Every bin is synthesised from m' = fma(l, x, c * e) -- two separate roundings, so (1, 0) returns x
+// and (0, 1) returns e bit for bit -- and the DC rule applies to m'; a held stream's noisy row is not read.  noisy and lim are null, and not
+// read, without MIX.  (The two magnitude rules stand side by side as they were written: the code the compiler makes of them is sensitive to it.)
+template <bool MIX>
 __global__ __launch_bounds__(256) void istft_hop_kernel(const float* __restrict__ est, const float2* __restrict__ ph,
                                                        const float* __restrict__ inv_win, const float2* __restrict__ tw,
                                                        float* __restrict__ ola, float* __restrict__ pcm_out, int dc_edge,
-                                                       const unsigned char* __restrict__ active) {
+                                                       const unsigned char* __restrict__ active, const float* __restrict__ noisy,
+                                                       const float2* __restrict__ lim) {
   __shared__ float re[N], im[N];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (active && !active[b]) {            // held stream (workgroup-uniform): a zero hop, its overlap tail stays
@@ -82,54 +88,28 @@ __global__ __launch_bounds__(256) void istft_hop_kernel(const float* __restrict_
     return;
   }
   const float* e = est + static_cast<size_t>(b) * H;
+  const float* x = MIX ? noisy + static_cast<size_t>(b) * H : nullptr;
+  const float2 lc = MIX ? lim[b] : make_float2(0.f, 1.f);
   const float2* p = ph + static_cast<size_t>(b) * (H + 1);
   // Hermitian spectrum: bins 0..256 given, 257..511 mirrored; irfft ignores the imaginary parts of bins 0 and 256
   {
     const int k = tid;                                   // bins 0..255
-    const float m = k == 0 ? (dc_edge ? e[0] : 0.f) : e[k - 1];
+    float m, m_top;                                      // the magnitudes of bin k and of bin 256
+    if constexpr (MIX) {
+      const int i = k == 0 ? 0 : k - 1;
+      const float mix = __fmaf_rn(lc.x, x[i], __fmul_rn(lc.y, e[i]));
+      m = k == 0 ? (dc_edge ? mix : 0.f) : mix;
+    } else {
+      m = k == 0 ? (dc_edge ? e[0] : 0.f) : e[k - 1];
+    }
     const float yr = m * p[k].x, yi = k == 0 ? 0.f : m * p[k].y;
     re[bitrev9(k)] = yr; im[bitrev9(k)] = yi;
     if (k >= 1) { re[bitrev9(N - k)] = yr; im[bitrev9(N - k)] = -yi; }
-    if (tid == 0) { re[bitrev9(H)] = e[H - 1] * p[H].x; im[bitrev9(H)] = 0.f; }
-  }
-  fft512(re, im, tw, tid, 1.f);
-  const float scale = 1.0f / static_cast<float>(N);
-  const float y0 = re[tid] * scale * inv_win[tid];
-  const float y1 = re[tid + H] * scale * inv_win[tid + H];
-  const size_t o = static_cast<size_t>(b) * H + tid;
-  pcm_out[o] = ola[o] + y0;
-  ola[o] = y1;
-}
-
-// istft_hop_kernel with an attenuation limit (nutls_set_atten_limit): noisy [B,256] the magnitudes of the same frame as stft_hop_kernel left
-// them, lim [B] = (l, c) with c = 1 - l formed on the host.  Every bin is synthesised from m' = fma(l, x, c * e) -- two separate roundings, so
-// (1, 0) returns x and (0, 1) returns e bit for bit -- and the DC rule applies to m'.  Everything else is the kernel above, statement for
-// statement; a held stream's noisy row is not read.
-__global__ __launch_bounds__(256) void istft_hop_mix_kernel(const float* __restrict__ est, const float* __restrict__ noisy,
-                                                           const float2* __restrict__ lim, const float2* __restrict__ ph,
-                                                           const float* __restrict__ inv_win, const float2* __restrict__ tw,
-                                                           float* __restrict__ ola, float* __restrict__ pcm_out, int dc_edge,
-                                                           const unsigned char* __restrict__ active) {
-  __shared__ float re[N], im[N];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (active && !active[b]) {            // held stream (workgroup-uniform): a zero hop, its overlap tail stays
-    pcm_out[static_cast<size_t>(b) * H + tid] = 0.f;
-    return;
-  }
-  const float* e = est + static_cast<size_t>(b) * H;
-  const float* x = noisy + static_cast<size_t>(b) * H;
-  const float2 lc = lim[b];
-  const float2* p = ph + static_cast<size_t>(b) * (H + 1);
-  // Hermitian spectrum: bins 0..256 given, 257..511 mirrored; irfft ignores the imaginary parts of bins 0 and 256
-  {
-    const int k = tid;                                   // bins 0..255
-    const int i = k == 0 ? 0 : k - 1;
-    const float mix = __fmaf_rn(lc.x, x[i], __fmul_rn(lc.y, e[i]));
-    const float m = k == 0 ? (dc_edge ? mix : 0.f) : mix;
-    const float yr = m * p[k].x, yi = k == 0 ? 0.f : m * p[k].y;
-    re[bitrev9(k)] = yr; im[bitrev9(k)] = yi;
-    if (k >= 1) { re[bitrev9(N - k)] = yr; im[bitrev9(N - k)] = -yi; }
-    if (tid == 0) { re[bitrev9(H)] = __fmaf_rn(lc.x, x[H - 1], __fmul_rn(lc.y, e[H - 1])) * p[H].x; im[bitrev9(H)] = 0.f; }
+    if (tid == 0) {
+      if constexpr (MIX) m_top = __fmaf_rn(lc.x, x[H - 1], __fmul_rn(lc.y, e[H - 1]));
+      else m_top = e[H - 1];
+      re[bitrev9(H)] = m_top * p[H].x; im[bitrev9(H)] = 0.f;
+    }
   }
   fft512(re, im, tw, tid, 1.f);
   const float scale = 1.0f / static_cast<float>(N);
@@ -147,17 +127,11 @@ hipError_t launch_stft_hop(const float* pcm, float* tail, const float* win, cons
   return hipGetLastError();
 }
 
-hipError_t launch_istft_hop(const float* est, const float* ph, const float* inv_win, const float* tw, float* ola, float* pcm_out,
-                            int dc_edge, int B, hipStream_t s, const unsigned char* active) {
-  hipLaunchKernelGGL(istft_hop_kernel, dim3(B), dim3(256), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
-                     reinterpret_cast<const float2*>(tw), ola, pcm_out, dc_edge, active);
-  return hipGetLastError();
-}
-
-hipError_t launch_istft_hop_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
-                                float* ola, float* pcm_out, int dc_edge, int B, hipStream_t s, const unsigned char* active) {
-  hipLaunchKernelGGL(istft_hop_mix_kernel, dim3(B), dim3(256), 0, s, est, noisy, reinterpret_cast<const float2*>(lim),
-                     reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola, pcm_out, dc_edge, active);
+hipError_t launch_istft_hop(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                            float* ola, float* pcm_out, int dc_edge, int B, hipStream_t s, const unsigned char* active) {
+  auto* kernel = noisy ? istft_hop_kernel<true> : istft_hop_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola,
+                     pcm_out, dc_edge, active, noisy, reinterpret_cast<const float2*>(lim));
   return hipGetLastError();
 }
 

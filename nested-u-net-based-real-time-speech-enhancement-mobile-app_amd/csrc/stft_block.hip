@@ -49,7 +49,6 @@
 #include <cmath>
 
 #include "nutls_internal.hpp"
-#include "ragged.hpp"
 #include "stft_wave.hpp"
 
 namespace nutls {
@@ -66,122 +65,38 @@ static_assert(kImage == kWaveImage, "the LDS image of a wave is the one stft_wav
 
 }  // namespace
 
-// grid (tiles of kWaves * kRun frames, U), 256 threads
+// Both kernels: grid (tiles of kWaves * kRun frames, U), 256 threads.  RAGGED (nutls_stft_block_ragged / nutls_istft_block_ragged): hops [U],
+// clamped to 0 .. n_hops -- utterance u has k = hops[u] real hops in a block whose row stride is n_hops.  A wave's run ends at hop k; the rows
+// behind it are written with zeros and never read; the carry is written by the wave that owns hop k - 1 (k = 0: the carried-in hop / overlap
+// tail is copied across, the two buffers alternate).  The counts change where a run ends and nothing else: every real hop goes through the one
+// loop body below, so it has the bits of the uniform block (tests/test_gpu_ragged_enhance.py).  hops is null, and not read, without RAGGED.
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * kWaves) void stft_block_kernel(const float* __restrict__ pcm, const float* __restrict__ tail_in,
                                                                  float* __restrict__ tail_out, const float* __restrict__ win,
                                                                  const float2* __restrict__ tw, float* __restrict__ mag,
-                                                                 float2* __restrict__ ph, int n_hops) {
-  __shared__ float2 image[kWaves][kImage];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
-  const int f0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;
-  if (f0 >= n_hops) return;
-  const int f1 = min(f0 + kRun, n_hops);
-  float2* buf = image[wave];
-  const Twiddles t = load_twiddles(tw, lane);
-  float2 w[4], ws[4];
-  load_analysis_regs(win, tw, lane, w, ws);
-  const size_t row0 = static_cast<size_t>(u) * n_hops;
-  const float2* prev = reinterpret_cast<const float2*>(f0 == 0 ? tail_in + static_cast<size_t>(u) * H : pcm + (row0 + f0 - 1) * H);
-  float2 p0 = prev[lane], p1 = prev[lane + 64];
-  const float2* cur = reinterpret_cast<const float2*>(pcm + (row0 + f0) * H);
-  float2 c0 = cur[lane], c1 = cur[lane + 64];
-#pragma unroll 1
-  for (int f = f0; f < f1; ++f) {
-    float2 n0 = c0, n1 = c1;
-    if (f + 1 < f1) {                                                          // the next hop is on its way while this frame is transformed
-      const float2* nxt = reinterpret_cast<const float2*>(pcm + (row0 + f + 1) * H);
-      n0 = nxt[lane]; n1 = nxt[lane + 64];
-    }
-    float m[4];
-    float2 rot[4], dc;
-    analyse_frame(p0, p1, c0, c1, w, ws, t, buf, lane, m, rot, dc);
-    const size_t row = row0 + f;
-    float2* mrow = reinterpret_cast<float2*>(mag + row * H);
-    mrow[lane] = make_float2(m[0], m[1]);
-    mrow[lane + 64] = make_float2(m[2], m[3]);
-    float2* prow = ph + row * (H + 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) prow[2 * lane + 1 + (i & 1) + 128 * (i >> 1)] = rot[i];
-    if (lane == 0) prow[0] = dc;
-    wave_sync();                                                               // (the reads above come before the next frame's writes)
-    p0 = c0; p1 = c1;
-    c0 = n0; c1 = n1;
-  }
-  if (f1 == n_hops) {                                                          // the last hop of the block is the next block's previous hop
-    float2* to = reinterpret_cast<float2*>(tail_out + static_cast<size_t>(u) * H);
-    to[lane] = p0; to[lane + 64] = p1;
-  }
-}
-
-__global__ __launch_bounds__(64 * kWaves) void istft_block_kernel(const float* __restrict__ est, const float2* __restrict__ ph,
-                                                                  const float* __restrict__ inv_win, const float2* __restrict__ tw,
-                                                                  const float* __restrict__ ola_in, float* __restrict__ ola_out,
-                                                                  float* __restrict__ pcm_out, int dc_edge, int n_hops) {
-  __shared__ float2 image[kWaves][kImage];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
-  const int o0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;      // this wave produces output hops [o0, o1)
-  if (o0 >= n_hops) return;
-  const int o1 = min(o0 + kRun, n_hops);
-  float2* buf = image[wave];
-  const Twiddles t = load_twiddles(tw, lane);
-  float2 iw[4], ws[4];
-  load_synthesis_regs(inv_win, tw, lane, iw, ws);
-  const size_t row0 = static_cast<size_t>(u) * n_hops;
-  float2 carry0 = make_float2(0.f, 0.f), carry1 = carry0;
-  if (o0 == 0) {
-    const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
-    carry0 = from[lane]; carry1 = from[lane + 64];
-  }
-  // frames o0 - 1 .. o1 - 1: the frame in front of the run only for its second half (the first run of a block has the carried one instead)
-#pragma unroll 1
-  for (int f = o0 > 0 ? o0 - 1 : 0; f < o1; ++f) {
-    const size_t row = row0 + f;
-    const float2* erow = reinterpret_cast<const float2*>(est + row * H);
-    const float2* prow = ph + row * (H + 1);
-    float2 v[4];
-    synthesise_frame(erow, prow, dc_edge, iw, ws, t, buf, lane, v);
-    if (f >= o0) {
-      float2* orow = reinterpret_cast<float2*>(pcm_out + row * H);
-      orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);
-      orow[lane + 64] = make_float2(carry1.x + v[1].x, carry1.y + v[1].y);
-    }
-    carry0 = v[2]; carry1 = v[3];
-    wave_sync();
-  }
-  if (o1 == n_hops) {
-    float2* to = reinterpret_cast<float2*>(ola_out + static_cast<size_t>(u) * H);
-    to[lane] = carry0; to[lane + 64] = carry1;
-  }
-}
-
-// ---- the same two kernels with per-utterance hop counts (nutls_stft_block_ragged / nutls_istft_block_ragged) ----
-// hops [U], clamped to 0 .. n_hops: utterance u has k = hops[u] real hops in a block whose row stride is n_hops.  A wave's run ends at hop k; the
-// rows behind it are written with zeros and never read; the carry is written by the wave that owns hop k - 1 (k = 0: the carried-in hop /
-// overlap tail is copied across, the two buffers alternate).  Every real hop goes through the loop body of the kernels above, statement for
-// statement: same bits (tests/test_gpu_ragged_enhance.py).  Kernels of their own, so that the uniform ones stay the code they were.
-__global__ __launch_bounds__(64 * kWaves) void stft_block_ragged_kernel(const float* __restrict__ pcm, const float* __restrict__ tail_in,
-                                                                        float* __restrict__ tail_out, const float* __restrict__ win,
-                                                                        const float2* __restrict__ tw, float* __restrict__ mag,
-                                                                        float2* __restrict__ ph, int n_hops, const int* __restrict__ hops) {
+                                                                 float2* __restrict__ ph, int n_hops, const int* __restrict__ hops) {
   __shared__ float2 image[kWaves][kImage];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
   const int f0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;
   if (f0 >= n_hops) return;
   int f1 = min(f0 + kRun, n_hops);
   const size_t row0 = static_cast<size_t>(u) * n_hops;
-  const int last = min(max(hops[u], 0), n_hops);                          // the carry is taken behind hop last - 1
-  for (int f = max(f0, last); f < f1; ++f) {
-    float2* mrow = reinterpret_cast<float2*>(mag + (row0 + f) * H);
-    mrow[lane] = make_float2(0.f, 0.f);
-    mrow[lane + 64] = make_float2(0.f, 0.f);
+  int last = n_hops;                                                           // the carry is taken behind hop last - 1
+  if constexpr (RAGGED) {
+    last = min(max(hops[u], 0), n_hops);
+    for (int f = max(f0, last); f < f1; ++f) {
+      float2* mrow = reinterpret_cast<float2*>(mag + (row0 + f) * H);
+      mrow[lane] = make_float2(0.f, 0.f);
+      mrow[lane + 64] = make_float2(0.f, 0.f);
+    }
+    if (last == 0 && f0 == 0) {
+      const float2* from = reinterpret_cast<const float2*>(tail_in + static_cast<size_t>(u) * H);
+      float2* to = reinterpret_cast<float2*>(tail_out + static_cast<size_t>(u) * H);
+      to[lane] = from[lane]; to[lane + 64] = from[lane + 64];
+    }
+    if (f0 >= last) return;
+    f1 = min(f1, last);
   }
-  if (last == 0 && f0 == 0) {
-    const float2* from = reinterpret_cast<const float2*>(tail_in + static_cast<size_t>(u) * H);
-    float2* to = reinterpret_cast<float2*>(tail_out + static_cast<size_t>(u) * H);
-    to[lane] = from[lane]; to[lane + 64] = from[lane + 64];
-  }
-  if (f0 >= last) return;
-  f1 = min(f1, last);
   float2* buf = image[wave];
   const Twiddles t = load_twiddles(tw, lane);
   float2 w[4], ws[4];
@@ -218,82 +133,26 @@ __global__ __launch_bounds__(64 * kWaves) void stft_block_ragged_kernel(const fl
   }
 }
 
-__global__ __launch_bounds__(64 * kWaves) void istft_block_ragged_kernel(const float* __restrict__ est, const float2* __restrict__ ph,
-                                                                         const float* __restrict__ inv_win, const float2* __restrict__ tw,
-                                                                         const float* __restrict__ ola_in, float* __restrict__ ola_out,
-                                                                         float* __restrict__ pcm_out, int dc_edge, int n_hops,
-                                                                         const int* __restrict__ hops) {
+// MIX, the attenuation limit (nutls_set_atten_limit / nutls_istft_block_mix): noisy [U][n_hops][256] the magnitudes of the same frames as the
+// analysis wrote them, lim [U] = (l, c) of each utterance, loaded once per wave.  Every frame is synthesised from m' = fma(l, x, c * e)
+// (synthesise_frame_mix); the noisy row of the redundant frame in front of a run is read again like its estimate, no row behind a count is read.
+// noisy and lim are null, and not read, without MIX.
+template <bool RAGGED, bool MIX>
+__global__ __launch_bounds__(64 * kWaves) void istft_block_kernel(const float* __restrict__ est, const float2* __restrict__ ph,
+                                                                  const float* __restrict__ inv_win, const float2* __restrict__ tw,
+                                                                  const float* __restrict__ ola_in, float* __restrict__ ola_out,
+                                                                  float* __restrict__ pcm_out, int dc_edge, int n_hops,
+                                                                  const int* __restrict__ hops, const float* __restrict__ noisy,
+                                                                  const float2* __restrict__ lim) {
   __shared__ float2 image[kWaves][kImage];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
   const int o0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;      // this wave produces output hops [o0, o1)
   if (o0 >= n_hops) return;
   int o1 = min(o0 + kRun, n_hops);
   const size_t row0 = static_cast<size_t>(u) * n_hops;
-  const int last = min(max(hops[u], 0), n_hops);                          // the carry is the second half of frame last - 1
-  for (int f = max(o0, last); f < o1; ++f) {
-    float2* orow = reinterpret_cast<float2*>(pcm_out + (row0 + f) * H);
-    orow[lane] = make_float2(0.f, 0.f);
-    orow[lane + 64] = make_float2(0.f, 0.f);
-  }
-  if (last == 0 && o0 == 0) {
-    const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
-    float2* to = reinterpret_cast<float2*>(ola_out + static_cast<size_t>(u) * H);
-    to[lane] = from[lane]; to[lane + 64] = from[lane + 64];
-  }
-  if (o0 >= last) return;
-  o1 = min(o1, last);
-  float2* buf = image[wave];
-  const Twiddles t = load_twiddles(tw, lane);
-  float2 iw[4], ws[4];
-  load_synthesis_regs(inv_win, tw, lane, iw, ws);
-  float2 carry0 = make_float2(0.f, 0.f), carry1 = carry0;
-  if (o0 == 0) {
-    const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
-    carry0 = from[lane]; carry1 = from[lane + 64];
-  }
-  // frames o0 - 1 .. o1 - 1: the frame in front of the run only for its second half (the first run of a block has the carried one instead)
-#pragma unroll 1
-  for (int f = o0 > 0 ? o0 - 1 : 0; f < o1; ++f) {
-    const size_t row = row0 + f;
-    const float2* erow = reinterpret_cast<const float2*>(est + row * H);
-    const float2* prow = ph + row * (H + 1);
-    float2 v[4];
-    synthesise_frame(erow, prow, dc_edge, iw, ws, t, buf, lane, v);
-    if (f >= o0) {
-      float2* orow = reinterpret_cast<float2*>(pcm_out + row * H);
-      orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);
-      orow[lane + 64] = make_float2(carry1.x + v[1].x, carry1.y + v[1].y);
-    }
-    carry0 = v[2]; carry1 = v[3];
-    wave_sync();
-  }
-  if (o1 == last) {
-    float2* to = reinterpret_cast<float2*>(ola_out + static_cast<size_t>(u) * H);
-    to[lane] = carry0; to[lane + 64] = carry1;
-  }
-}
-
-// ---- the two synthesis kernels with an attenuation limit (nutls_set_atten_limit / nutls_istft_block_mix) ----
-// noisy [U][n_hops][256]: the magnitudes of the same frames as the analysis wrote them; lim [U] = (l, c) of each utterance, loaded once per wave.
-// Every frame is synthesised from m' = fma(l, x, c * e) (synthesise_frame_mix); runs, tiles and carry are those of the kernels above, RAGGED
-// their ragged twin: the noisy row of the redundant frame in front of a run is read again like its estimate, no row behind a count is read.
-// Kernels of their own, so that the four above stay the code they were.
-template <bool RAGGED>
-__global__ __launch_bounds__(64 * kWaves) void istft_block_mix_kernel(const float* __restrict__ est, const float* __restrict__ noisy,
-                                                                      const float2* __restrict__ lim, const float2* __restrict__ ph,
-                                                                      const float* __restrict__ inv_win, const float2* __restrict__ tw,
-                                                                      const float* __restrict__ ola_in, float* __restrict__ ola_out,
-                                                                      float* __restrict__ pcm_out, int dc_edge, int n_hops,
-                                                                      const int* __restrict__ hops) {
-  __shared__ float2 image[kWaves][kImage];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = blockIdx.y;
-  const int o0 = (static_cast<int>(blockIdx.x) * kWaves + wave) * kRun;      // this wave produces output hops [o0, o1)
-  if (o0 >= n_hops) return;
-  int o1 = min(o0 + kRun, n_hops);
-  const size_t row0 = static_cast<size_t>(u) * n_hops;
-  int last = n_hops;
-  if (RAGGED) {
-    last = min(max(hops[u], 0), n_hops);                                     // the carry is the second half of frame last - 1
+  int last = n_hops;                                                           // the carry is the second half of frame last - 1
+  if constexpr (RAGGED) {
+    last = min(max(hops[u], 0), n_hops);
     for (int f = max(o0, last); f < o1; ++f) {
       float2* orow = reinterpret_cast<float2*>(pcm_out + (row0 + f) * H);
       orow[lane] = make_float2(0.f, 0.f);
@@ -311,7 +170,8 @@ __global__ __launch_bounds__(64 * kWaves) void istft_block_mix_kernel(const floa
   const Twiddles t = load_twiddles(tw, lane);
   float2 iw[4], ws[4];
   load_synthesis_regs(inv_win, tw, lane, iw, ws);
-  const float2 lc = lim[u];
+  float2 lc = make_float2(0.f, 1.f);
+  if constexpr (MIX) lc = lim[u];
   float2 carry0 = make_float2(0.f, 0.f), carry1 = carry0;
   if (o0 == 0) {
     const float2* from = reinterpret_cast<const float2*>(ola_in + static_cast<size_t>(u) * H);
@@ -322,10 +182,10 @@ __global__ __launch_bounds__(64 * kWaves) void istft_block_mix_kernel(const floa
   for (int f = o0 > 0 ? o0 - 1 : 0; f < o1; ++f) {
     const size_t row = row0 + f;
     const float2* erow = reinterpret_cast<const float2*>(est + row * H);
-    const float2* xrow = reinterpret_cast<const float2*>(noisy + row * H);
     const float2* prow = ph + row * (H + 1);
     float2 v[4];
-    synthesise_frame_mix(erow, xrow, lc, prow, dc_edge, iw, ws, t, buf, lane, v);
+    if constexpr (MIX) synthesise_frame_mix(erow, reinterpret_cast<const float2*>(noisy + row * H), lc, prow, dc_edge, iw, ws, t, buf, lane, v);
+    else synthesise_frame(erow, prow, dc_edge, iw, ws, t, buf, lane, v);
     if (f >= o0) {
       float2* orow = reinterpret_cast<float2*>(pcm_out + row * H);
       orow[lane] = make_float2(carry0.x + v[0].x, carry0.y + v[0].y);
@@ -358,42 +218,21 @@ std::vector<float> stft_block_twiddles() {
 
 static dim3 block_grid(int U, int n_hops) { return dim3((n_hops + kWaves * kRun - 1) / (kWaves * kRun), U); }
 
+// The instantiation follows from which of the optional pointers are given (nutls_internal.hpp).
 hipError_t launch_stft_block(const float* pcm, const float* tail_in, float* tail_out, const float* win, const float* tw, float* mag, float* ph,
-                             int U, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL(stft_block_kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, pcm, tail_in, tail_out, win,
-                     reinterpret_cast<const float2*>(tw), mag, reinterpret_cast<float2*>(ph), n_hops);
+                             const int* hops, int U, int n_hops, hipStream_t s) {
+  auto* kernel = hops ? stft_block_kernel<true> : stft_block_kernel<false>;
+  hipLaunchKernelGGL(kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, pcm, tail_in, tail_out, win, reinterpret_cast<const float2*>(tw), mag,
+                     reinterpret_cast<float2*>(ph), n_hops, hops);
   return hipGetLastError();
 }
 
-hipError_t launch_istft_block(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
-                              float* pcm_out, int dc_edge, int U, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL(istft_block_kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
-                     reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops);
-  return hipGetLastError();
-}
-
-hipError_t launch_stft_block_ragged(const float* pcm, const float* tail_in, float* tail_out, const float* win, const float* tw, float* mag, float* ph,
-                                    const int* hops, int U, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL(stft_block_ragged_kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, pcm, tail_in, tail_out, win,
-                     reinterpret_cast<const float2*>(tw), mag, reinterpret_cast<float2*>(ph), n_hops, hops);
-  return hipGetLastError();
-}
-
-hipError_t launch_istft_block_ragged(const float* est, const float* ph, const float* inv_win, const float* tw, const float* ola_in, float* ola_out,
-                                     float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s) {
-  hipLaunchKernelGGL(istft_block_ragged_kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
-                     reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
-  return hipGetLastError();
-}
-
-hipError_t launch_istft_block_mix(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
-                                  const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s) {
-  if (hops)
-    hipLaunchKernelGGL(istft_block_mix_kernel<true>, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, noisy, reinterpret_cast<const float2*>(lim),
-                       reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
-  else
-    hipLaunchKernelGGL(istft_block_mix_kernel<false>, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, noisy, reinterpret_cast<const float2*>(lim),
-                       reinterpret_cast<const float2*>(ph), inv_win, reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops);
+hipError_t launch_istft_block(const float* est, const float* noisy, const float* lim, const float* ph, const float* inv_win, const float* tw,
+                              const float* ola_in, float* ola_out, float* pcm_out, int dc_edge, const int* hops, int U, int n_hops, hipStream_t s) {
+  auto* kernel = noisy ? (hops ? istft_block_kernel<true, true> : istft_block_kernel<false, true>)
+                       : (hops ? istft_block_kernel<true, false> : istft_block_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, block_grid(U, n_hops), dim3(64 * kWaves), 0, s, est, reinterpret_cast<const float2*>(ph), inv_win,
+                     reinterpret_cast<const float2*>(tw), ola_in, ola_out, pcm_out, dc_edge, n_hops, hops, noisy, reinterpret_cast<const float2*>(lim));
   return hipGetLastError();
 }
 

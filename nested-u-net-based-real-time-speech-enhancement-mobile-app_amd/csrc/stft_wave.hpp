@@ -115,53 +115,13 @@ __device__ __forceinline__ void analyse_frame(float2 p0, float2 p1, float2 c0, f
   dc = make_float2(x0 < 0.f ? -1.f : 1.f, 0.f);
 }
 
-// Synthesis of one frame.  erow: the 256 estimates (bins 1..256), prow: the 257 phasors of the same frame; iw: inverse-window taps 2 l + 128 a, + 1;
-// ws: conj W512^k, k = l + 64 a.  Out: v[a] = samples 2 l + 128 a, + 1 of the windowed inverse transform (v[0], v[1]: first half, added to the
-// overlap tail; v[2], v[3]: second half, the next tail).  Leaves the image in use: wave_sync() before the next write.
-__device__ __forceinline__ void synthesise_frame(const float2* __restrict__ erow, const float2* __restrict__ prow, int dc_edge, const float2 (&iw)[4],
-                                                 const float2 (&ws)[4], const Twiddles& t, float2* buf, int lane, float2 (&v)[4]) {
+// Synthesis of one frame from the four magnitudes es of the lane's bins 2 l + 1, 2 l + 2 (+ 128), whoever formed them.  prow: the 257 phasors of the
+// frame; iw: inverse-window taps 2 l + 128 a, + 1; ws: conj W512^k, k = l + 64 a.  Out: v[a] = samples 2 l + 128 a, + 1 of the windowed inverse
+// transform (v[0], v[1]: first half, added to the overlap tail; v[2], v[3]: second half, the next tail).  The DC rule takes the magnitude of bin 1.
+// Leaves the image in use: wave_sync() before the next write.
+__device__ __forceinline__ void synthesise_bins(const float (&es)[4], const float2* __restrict__ prow, int dc_edge, const float2 (&iw)[4],
+                                                const float2 (&ws)[4], const Twiddles& t, float2* buf, int lane, float2 (&v)[4]) {
   const float scale = 1.0f / static_cast<float>(NUTLS_FRAME_LEN);
-  const float2 e0 = erow[lane], e1 = erow[lane + 64];                        // bins 2 l + 1, 2 l + 2 (+ 128)
-  const float es[4] = {e0.x, e0.y, e1.x, e1.y};
-  // Hermitian spectrum: bins 0..256 given, the rest mirrored; the imaginary parts of bins 0 and 256 are ignored
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k = 2 * lane + 1 + (i & 1) + 128 * (i >> 1);
-    const float2 r = prow[k];
-    buf[k == 256 ? 256 : spec(k)] = make_float2(es[i] * r.x, k == 256 ? 0.f : es[i] * r.y);
-  }
-  if (lane == 0) buf[0] = make_float2(dc_edge ? e0.x * prow[0].x : 0.f, 0.f);
-  wave_sync();
-  float2 x[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const int k = lane + 64 * a;
-    const float2 yk = buf[spec(k)], ym = buf[k == 0 ? 256 : spec(256 - k)];
-    const float2 e = make_float2(yk.x + ym.x, yk.y - ym.y);
-    const float2 o = cmul(make_float2(yk.x - ym.x, yk.y + ym.y), ws[a]);
-    x[a] = make_float2(e.y + o.x, e.x - o.y);                                // Z = E + i O, re / im swapped: the inverse transform
-  }
-  wave_sync();
-  fft256(x, buf, t, lane);
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const float2 z = buf[nat(lane + 64 * a)];                                // (swapped back: .y = sample 2 n, .x = sample 2 n + 1)
-    v[a] = make_float2(z.y * scale * iw[a].x, z.x * scale * iw[a].y);
-  }
-}
-
-// synthesise_frame with an attenuation limit (nutls_set_atten_limit): xrow the noisy magnitudes of the same frame, lc = (l, c) of its row with
-// c = 1 - l formed on the host.  Where the body above reads es[i] this one reads m' = fma(l, x, c * e), two separate roundings -- (1, 0) gives x
-// and (0, 1) gives e bit for bit; the DC rule takes m' of bin 1.  Every other statement is the body above (which the hop builds of the step
-// kernel use, and which therefore stays as it is).
-__device__ __forceinline__ void synthesise_frame_mix(const float2* __restrict__ erow, const float2* __restrict__ xrow, float2 lc,
-                                                     const float2* __restrict__ prow, int dc_edge, const float2 (&iw)[4], const float2 (&ws)[4],
-                                                     const Twiddles& t, float2* buf, int lane, float2 (&v)[4]) {
-  const float scale = 1.0f / static_cast<float>(NUTLS_FRAME_LEN);
-  const float2 e0 = erow[lane], e1 = erow[lane + 64];                        // bins 2 l + 1, 2 l + 2 (+ 128)
-  const float2 x0 = xrow[lane], x1 = xrow[lane + 64];
-  const float es[4] = {__fmaf_rn(lc.x, x0.x, __fmul_rn(lc.y, e0.x)), __fmaf_rn(lc.x, x0.y, __fmul_rn(lc.y, e0.y)),
-                       __fmaf_rn(lc.x, x1.x, __fmul_rn(lc.y, e1.x)), __fmaf_rn(lc.x, x1.y, __fmul_rn(lc.y, e1.y))};
   // Hermitian spectrum: bins 0..256 given, the rest mirrored; the imaginary parts of bins 0 and 256 are ignored
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -187,6 +147,26 @@ __device__ __forceinline__ void synthesise_frame_mix(const float2* __restrict__ 
     const float2 z = buf[nat(lane + 64 * a)];                                // (swapped back: .y = sample 2 n, .x = sample 2 n + 1)
     v[a] = make_float2(z.y * scale * iw[a].x, z.x * scale * iw[a].y);
   }
+}
+
+// erow: the 256 estimates of the frame (bins 1..256), synthesised as they are.  (The hop builds of the step kernel call this one.)
+__device__ __forceinline__ void synthesise_frame(const float2* __restrict__ erow, const float2* __restrict__ prow, int dc_edge, const float2 (&iw)[4],
+                                                 const float2 (&ws)[4], const Twiddles& t, float2* buf, int lane, float2 (&v)[4]) {
+  const float2 e0 = erow[lane], e1 = erow[lane + 64];                        // bins 2 l + 1, 2 l + 2 (+ 128)
+  const float es[4] = {e0.x, e0.y, e1.x, e1.y};
+  synthesise_bins(es, prow, dc_edge, iw, ws, t, buf, lane, v);
+}
+
+// With an attenuation limit (nutls_set_atten_limit): xrow the noisy magnitudes of the same frame, lc = (l, c) of its row with c = 1 - l formed
+// on the host.  Every bin is synthesised from m' = fma(l, x, c * e), two separate roundings -- (1, 0) gives x and (0, 1) gives e bit for bit.
+__device__ __forceinline__ void synthesise_frame_mix(const float2* __restrict__ erow, const float2* __restrict__ xrow, float2 lc,
+                                                     const float2* __restrict__ prow, int dc_edge, const float2 (&iw)[4], const float2 (&ws)[4],
+                                                     const Twiddles& t, float2* buf, int lane, float2 (&v)[4]) {
+  const float2 e0 = erow[lane], e1 = erow[lane + 64];                        // bins 2 l + 1, 2 l + 2 (+ 128)
+  const float2 x0 = xrow[lane], x1 = xrow[lane + 64];
+  const float es[4] = {__fmaf_rn(lc.x, x0.x, __fmul_rn(lc.y, e0.x)), __fmaf_rn(lc.x, x0.y, __fmul_rn(lc.y, e0.y)),
+                       __fmaf_rn(lc.x, x1.x, __fmul_rn(lc.y, e1.x)), __fmaf_rn(lc.x, x1.y, __fmul_rn(lc.y, e1.y))};
+  synthesise_bins(es, prow, dc_edge, iw, ws, t, buf, lane, v);
 }
 
 // the window / split-pass registers of a wave (analysis: win and W512^k of the lane's four bins; synthesis: inverse window and conj W512^(l + 64 a))

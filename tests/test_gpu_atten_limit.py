@@ -1,5 +1,5 @@
-"""``-m gpu``: the attenuation limit (include/nutls.h, "Attenuation limit") -- ``istft_hop_mix_kernel`` (csrc/stft.hip) and
-``istft_block_mix_kernel`` with its ragged twin (csrc/stft_block.hip on ``synthesise_frame_mix`` of csrc/stft_wave.hpp) against the float64
+"""``-m gpu``: the attenuation limit (include/nutls.h, "Attenuation limit") -- ``istft_hop_kernel<true>`` (csrc/stft.hip) and
+``istft_block_kernel<RAGGED, true>``, uniform and ragged (csrc/stft_block.hip on ``synthesise_frame_mix`` of csrc/stft_wave.hpp) against the float64
 synthesis of the rows mixed in double, on the designed signals and estimates of tests/transform_signals.py with the limits ``L`` of
 tests/atten_limit_reference.py; the exact ends inside one launch; the same bits however the audio is cut; and, with the model in between,
 limit 0 as the path it was, linearity in the limit, masks, settings, refusals and the corpus scheduler.
@@ -166,13 +166,13 @@ def check_against_float64(what, run, streams=None):
 
 # ---- 1, 2. against float64 -------------------------------------------------------------------------------------------------------------
 def test_per_hop_mix_kernel_against_float64(per_hop):
-    """istft_hop_mix_kernel, 8 streams with the limits L x 48 hops, both DC modes.  The mix adds two roundings, at most
+    """istft_hop_kernel<true>, 8 streams with the limits L x 48 hops, both DC modes.  The mix adds two roundings, at most
     2^-23 (l |x| + c |e|) per bin: under 6 % of the bound."""
     check_against_float64("per-hop mix kernel", per_hop)
 
 
 def test_block_mix_kernel_against_float64(block):
-    """istft_block_mix_kernel<false>, one call of 48 hops of 8 utterances (three tiles of four runs each)."""
+    """istft_block_kernel<false, true>, one call of 48 hops of 8 utterances (three tiles of four runs each)."""
     check_against_float64("block mix kernel", block)
 
 
@@ -214,7 +214,7 @@ def test_block_mix_kernel_cut_across_runs_and_tiles_gives_the_same_bits(offline,
 
 
 def test_ragged_mix_kernel_is_the_uniform_one_in_front_of_each_count(offline, block):
-    """istft_block_mix_kernel<true> with counts 48, 1, 17, 0, 16, 5, 33, 4 and NaN in every estimate, noisy and PCM row behind a count: the
+    """istft_block_kernel<true, true> with counts 48, 1, 17, 0, 16, 5, 33, 4 and NaN in every estimate, noisy and PCM row behind a count: the
     uniform call's bits in front of each count, zeros behind it.  Utterance 3 (count 0) keeps its overlap tail: a uniform call of 8 hops
     afterwards gives it the first 8 hops of the uniform run, as if the ragged block had not been there."""
     _, _, pcm = block[:3]
@@ -231,16 +231,8 @@ def test_ragged_mix_kernel_is_the_uniform_one_in_front_of_each_count(offline, bl
 
 
 # ---- 5. per-hop against block ----------------------------------------------------------------------------------------------------------
-def strong_estimates():
-    """``estimates()`` on the bins whose phasor a transform defines (tests/test_gpu_transforms.py, ``strong_estimates``): the two families
-    give the bins that hold rounding noise alone unrelated phasors."""
-    X = TS.analysis_reference()
-    keep = (np.abs(X) > TS.STRONG * TS.frame_scales(X)[..., None])[..., 1:]
-    return np.ascontiguousarray(TS.estimates() * keep)
-
-
 def test_block_mix_kernel_agrees_with_the_per_hop_mix_kernel(offline):
-    est = strong_estimates()
+    est = TS.strong_estimates()          # (the two families give the bins that hold rounding noise alone unrelated phasors)
     _, _, xb, _ = block_run(offline, [N], A.L, est=est)
     _, _, xh, _ = per_hop_run(range(8), A.L, est=est)
     led = TS.Ledger("block against per-hop mix kernel")

@@ -1,5 +1,5 @@
 """``-m gpu``: the three implementations of the 512-point analysis and synthesis -- the per-hop kernels (csrc/stft.hip: radix-2 in LDS), the
-block kernels and their ragged twins (csrc/stft_block.hip on csrc/stft_wave.hpp: radix-4 in registers) and the hop builds of the fused step
+block kernels, uniform and ragged (csrc/stft_block.hip on csrc/stft_wave.hpp: radix-4 in registers) and the hop builds of the fused step
 (csrc/fused_step.hip, FZ_HOP: the same header, their own loads, stores and LDS placement) -- against ``np.fft`` in double on the designed
 signals and estimates of tests/transform_signals.py, PER FRAME and PER OUTPUT HOP: MAG x the frame's own scale on magnitudes, PHASOR on the
 bins that are strong in their own frame, SYNTH x the output hop's own normaliser, and the exact conditions (an empty frame gives 0 and (1, 0),
@@ -150,7 +150,7 @@ def check_against_float64(what, mag, ph, pcm, streams=None, n=N):
 
 # ---- a, b. per-hop kernels -------------------------------------------------------------------------------------------------------------
 def test_per_hop_kernels_against_float64(per_hop):
-    """stft_hop_kernel / istft_hop_kernel, 8 streams x 48 hops: analysis per frame, synthesis of ``estimates()`` per output hop in both DC
+    """stft_hop_kernel / istft_hop_kernel<false>, 8 streams x 48 hops: analysis per frame, synthesis of ``estimates()`` per output hop in both DC
     modes on the phasors read back, and edge - zero against the reference's difference (the DC term: est[0] x Re phasor[0] / 512 x the
     inverse window -- a flipped DC sign doubles it)."""
     mag, ph, pcm = per_hop
@@ -168,7 +168,7 @@ def test_per_hop_kernels_with_an_odd_batch_give_the_same_bits(per_hop):
 
 # ---- c. block kernels ------------------------------------------------------------------------------------------------------------------
 def test_block_kernels_against_float64(block):
-    """stft_block_kernel / istft_block_kernel, one call of 48 hops of 8 utterances (three tiles of four runs each)."""
+    """stft_block_kernel<false> / istft_block_kernel<false, false>, one call of 48 hops of 8 utterances (three tiles of four runs each)."""
     mag, ph, pcm = block
     check_against_float64("block kernels", mag, ph, pcm)
 
@@ -182,23 +182,12 @@ def test_block_kernels_cut_across_runs_and_tiles_give_the_same_bits(offline, blo
         assert np.array_equal(x[dc], pcm[dc]), dc
 
 
-def strong_estimates():
-    """``estimates()`` with the bins zeroed whose phasor no transform defines: |X_f,k| <= STRONG x scale_f in the float64 reference.  (On
-    dc_neg, nyquist and sine most bins of most frames hold rounding noise alone; two device paths give them unrelated phasors, and a
-    waveform synthesised from estimates on those bins differs by its own size whatever the kernels do.  The comparison with float64 above
-    does not need this: there each path is referenced on its own phasors.)"""
-    X = TS.analysis_reference()
-    absX, scale = np.abs(X), TS.frame_scales(X)
-    keep = (absX > TS.STRONG * scale[..., None])[..., 1:]
-    return np.ascontiguousarray(TS.estimates() * keep)
-
-
 def test_block_kernels_agree_with_the_per_hop_kernels(offline, block, per_hop):
     """Relative RMS per stream at DEVICE_REL: magnitudes (every stream by its own RMS), and the waveforms of both DC modes synthesised from
     the estimates on the strong bins (``strong_estimates``) by both families, each on its own phasors."""
     led = TS.Ledger("block against per-hop kernels")
     led.device("magnitudes", block[0], per_hop[0])
-    est = strong_estimates()
+    est = TS.strong_estimates()
     _, _, xb = block_run(offline, [N], est=est)
     _, _, xh = per_hop_run(range(8), est=est)
     for dc in DCS:
@@ -213,7 +202,7 @@ def test_block_kernels_agree_with_the_per_hop_kernels(offline, block, per_hop):
 
 # ---- d. ragged block kernels -----------------------------------------------------------------------------------------------------------
 def test_ragged_block_kernels_are_the_uniform_ones_in_front_of_each_count(offline, block):
-    """stft_block_ragged_kernel / istft_block_ragged_kernel with counts 48, 1, 17, 0, 16, 5, 33, 4 (NaN behind every count): the rows in
+    """stft_block_kernel<true> / istft_block_kernel<true, false> with counts 48, 1, 17, 0, 16, 5, 33, 4 (NaN behind every count): the rows in
     front of a count carry the bits of the uniform call, the rows behind it are zeros.  Then a second ragged call that holds every other
     utterance (count 0: on a previous hop and an overlap tail that are not zero any more, except the one that never started) and gives
     the rest 8 more hops, and a uniform call of 8 hops: every utterance goes on with the bits of the uniform 48-hop call from where its

@@ -198,6 +198,14 @@ def strong_bins(X):
     return np.abs(X) > STRONG * frame_scales(X)[..., None]
 
 
+def strong_estimates():
+    """``estimates()`` with the bins zeroed whose phasor no transform defines: |X_f,k| <= STRONG x scale_f in the float64 reference.  (On
+    dc_neg, nyquist and sine most bins of most frames hold rounding noise alone; two device paths give them unrelated phasors, and a
+    waveform synthesised from estimates on those bins differs by its own size whatever the kernels do.  A comparison with float64 does not
+    need this: there each path is referenced on its own phasors.)"""
+    return np.ascontiguousarray(estimates() * strong_bins(analysis_reference())[..., 1:])
+
+
 def rel_rms(got, want):
     """Relative RMS of one stream (DEVICE_REL): RMS of the difference over the RMS of ``want``."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)

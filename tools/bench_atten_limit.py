@@ -1,6 +1,6 @@
 """What the attenuation limit (nutls_set_atten_limit) costs: nutls_enhance_hop at B = 256 in ms per hop and nutls_enhance_block at 8 utterances
-x 1 024 hops in ms per block, with every limit 0 (the kernels every entry always launched), with every limit 0.1 (the synthesis runs its mix
-twin, csrc/stft.hip / csrc/stft_block.hip: one more magnitude row read per stream and hop) and with the PARENT commit's library.
+x 1 024 hops in ms per block, with every limit 0 (the kernels every entry always launched), with every limit 0.1 (the synthesis runs its MIX
+instantiation, csrc/stft.hip / csrc/stft_block.hip: one more magnitude row read per stream and hop) and with the PARENT commit's library.
 
     python tools/bench_atten_limit.py [--parent-lib PATH] [--out profiles/atten_limit_bench.json]
 
