@@ -546,6 +546,44 @@ int nutls_pcm_packet_last_rounds(nutls_handle* h);           /* hop rounds the l
 int nutls_enhance_packet_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream);
 int nutls_enhance_packet_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode);
 
+/* ---- Channels: interleaved 2- and 4-channel audio, one stream per channel ----------------------------------------------------------
+ * The audio the formats above were built for rarely arrives one row per talker: a call-centre archive is a stereo file with the agent on the
+ * left and the customer on the right, a WebRTC or Opus decoder hands over interleaved stereo, a wave-file reader returns [N, C].  The channels
+ * of such a frame are what a handle's streams are -- independent talkers with their own model state --, so a handle can be told that its
+ * callers' buffers hold C channels per frame, and the split and the join happen on the device, beside the conversions.
+ *   The layout (the contract).  B is the handle's rows: the streams of a streaming handle, the utterances of an offline one.  While C > 1
+ *   the callers' side of EVERY _pcm entry is [B / C, n * C] of the handle's sample type, and sample i of stream r * C + c is at column
+ *   i * C + c of row r: channel c of frame row r is stream r * C + c.  This covers the four hop entries, nutls_pcm_decode_hop /
+ *   nutls_pcm_encode_hop, the block entries and their halves, the _ragged forms, nutls_enhance_packet_pcm and its _host form; n is S
+ *   (nutls_pcm_hop_samples), n_hops * S or P.  The base pointer is 16-byte aligned as before; rows stay multiples of 16 bytes because
+ *   S * bytes and P * bytes already are.  The 16 kHz float side of the halves stays [B, 256] and [utterances, n_hops * 256], one row per stream.
+ *   Everything else is per stream, as it was: `active` is [B] bytes, `hops` is [B] counts -- the channels of one frame row may have different
+ *   counts, 0 included --, and the attenuation limit, nutls_pcm_follow_gain, nutls_pcm_packet_fill and nutls_reset(h, b) work per stream.
+ *   A held stream's samples, and the hops behind a count, now sit in the same 16-byte words as their partner's: they are read as bytes,
+ *   HAVE NO EFFECT and may hold anything, NaN included (where this header says "is not read" of such samples, read "has no effect" while
+ *   C > 1).  On the way out they carry what the 1-channel entry writes there: zeros, or the law's silence code 0xFF / 0xD5.
+ *   THE RULE: for every entry E, E_C(x) == interleave(E_1(deinterleave(x))) in every bit -- outputs and all carried state.
+ *   nutls_set_pcm_channels(h, C): 1 = off (the default), 2 or 4, which need B % C == 0.  Any other value, a B that C does not divide or a
+ *   null handle is NUTLS_ERR_ARG; nutls_last_error names the entry and nothing changes.  It is a setting, not stream state, like the
+ *   attenuation limit: it may be called between any two calls, synchronises the device, touches no history, FIFO, model state, upper-band
+ *   or follow state, and survives nutls_reset and nutls_set_pcm_format.  So a stream's concatenated output does not depend on the layout its
+ *   hops arrived in, and the layout may change in mid-stream.  Setting the value in force is a no-op.  nutls_pcm_channels = C.
+ *   pcm_in == pcm_out (the same base pointer) stays allowed: the input is split into a library buffer before anything writes the output.
+ *   With C == 1 every entry launches exactly the kernels it launched before this section existed, same bits.  With C > 1 an entry is a
+ *   split launch, the 1-channel entry on library buffers, a join launch -- at 16000 / NUTLS_PCM_F32 too, where the 1-channel entry is the
+ *   plain float one.  Refusals are checked before anything is split: a refused call changes nothing.  The _host entries copy the interleaved
+ *   bytes through their staging (the byte count is the same) and take the device path.  The plain float entries (nutls_enhance_hop,
+ *   nutls_enhance_block, the nutls_stft_ and nutls_step families) ignore the setting, as they ignore the format.
+ *   nutls_pcm_deinterleave / nutls_pcm_interleave are the library's statement of the rule, host only, with no handle and no GPU, as
+ *   nutls_pcm_g711_expand is: frames [n, C] -> rows [C, n] and back, samples of 4, 2, 1, 1 bytes for NUTLS_PCM_F32, _S16, _ULAW, _ALAW, moved as
+ *   bytes.  Any n >= 0 is accepted; the two buffers must not overlap.  Channels other than 2 or 4, an unknown format or a null pointer is
+ *   NUTLS_ERR_ARG and nothing is written.  The kernels agree with them bit for bit.
+ *   Cost: two small launches per call, which move every byte once each way; measured: README, "Channels". */
+int nutls_set_pcm_channels(nutls_handle* h, int channels);   /* 1 = off (the default), 2 or 4 */
+int nutls_pcm_channels(nutls_handle* h);
+int nutls_pcm_deinterleave(int sample_format, int channels, const void* frames, void* rows, size_t n);  /* host only, no handle: [n, C] -> [C, n] */
+int nutls_pcm_interleave(int sample_format, int channels, const void* rows, void* frames, size_t n);    /* host only, no handle: [C, n] -> [n, C] */
+
 /* ---- Attenuation limit: a per-row cap on how much noise is removed ------------------------------------------------------
  * Every waveform entry returns the model's full suppression by default.  With a limit l in 0 .. 1 on a row (a stream of a streaming handle,
  * an utterance of an offline one) the synthesis mixes, per bin 1..256 of every frame, the noisy magnitude x of that frame (as the analysis

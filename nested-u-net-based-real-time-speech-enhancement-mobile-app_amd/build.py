@@ -19,13 +19,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libnutls_hip.so")
-SOURCES = ["fused_step.hip", "fused_step_g2.hip", "fused_step_g4.hip", "fused_step_hop.hip", "fused_step_g2_hop.hip", "fused_step_prof.hip", "fused_step_stop.hip", "fused_base.hip", "fused_base_prof.hip", "kernels.hip", "stft.hip", "stft_block.hip", "ragged.hip", "pcm.hip", "packet.hip", "offline.hip", "weights.cpp", "fused_host.cpp", "engine.cpp", "api_stream.cpp", "api_block.cpp", "api_state.cpp", "api_profile.cpp", "api_pcm.cpp"]
+SOURCES = ["fused_step.hip", "fused_step_g2.hip", "fused_step_g4.hip", "fused_step_hop.hip", "fused_step_g2_hop.hip", "fused_step_prof.hip", "fused_step_stop.hip", "fused_base.hip", "fused_base_prof.hip", "kernels.hip", "stft.hip", "stft_block.hip", "ragged.hip", "pcm.hip", "packet.hip", "channels.hip", "offline.hip", "weights.cpp", "fused_host.cpp", "engine.cpp", "api_stream.cpp", "api_block.cpp", "api_state.cpp", "api_profile.cpp", "api_pcm.cpp"]
 if os.environ.get("NUTLS_BUILD_G4_PROF") == "1":      # developer knob: the profiling twin of the 4-stream packed kernel (12 more minutes)
     SOURCES.insert(3, "fused_step_g4_prof.hip")
 # (fused_step_hop.hip / fused_step_g2_hop.hip: the hop builds of the one- and two-stream kernels, nutls_set_hop_fusion)
 # (ragged.hip: the stage-in / commit kernels of the ragged block calls, nutls_process_block_ragged)
 # (pcm.hip + api_pcm.cpp: the PCM gateway -- the callers' sample rate and sample type converted on the device, nutls_set_pcm_format)
 # (packet.hip: packet mode of the PCM gateway -- the callers' 10 / 20 ms packets re-framed into hops on the device, nutls_set_pcm_packet)
+# (channels.hip: channels of the PCM gateway -- interleaved 2- and 4-channel frames split into one row per stream and joined back, nutls_set_pcm_channels)
 # (engine.cpp + api_stream.cpp / api_block.cpp / api_state.cpp / api_profile.cpp: the host engine and the entry points of the C ABI by family; they share engine.hpp)
 # (headers are found by scanning the #include "..." lines of every source: _deps)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

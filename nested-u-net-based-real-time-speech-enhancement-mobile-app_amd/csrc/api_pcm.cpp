@@ -9,6 +9,8 @@
 // follow (nutls_set_pcm_upper_follow): on top of that, the gain follows the model.  With a gain of 0 / follow off nothing here differs.
 // G.711 (NUTLS_PCM_ULAW / NUTLS_PCM_ALAW, 8000 Hz only): a format like the others -- nutls_set_pcm_format validates it, sample_bytes is 1, the
 // launch gets the format code; nothing else here knows.  The rule itself is stated once on the host (g711_expand / g711_compress below).
+// Channels (nutls_set_pcm_channels): with more than one the callers' side of every entry is interleaved frame rows; through_channels splits it
+// into one row per stream in front of the path above and joins the result behind it (channels.hip) -- at 16000 / float32 too, around the plain entry.
 // The kernel template, its 36 instantiations and the one place that picks among them: pcm.hip.
 #include <algorithm>
 #include <cstdint>
@@ -163,10 +165,64 @@ int pcm_ready(Engine* e) {
   return pcm_init(e);
 }
 
-// what the entries of one half on its own do behind their refusals
+// ---- channels (nutls.h, "Channels"; the kernels: channels.hip) ------------------------------------------------------------------------------
+int grow_pair(Engine* e, size_t bytes, unsigned char** a, unsigned char** b, size_t* cap);      // (below, with packet mode)
+
+int handle_rows(const Engine* e) { return e->offline ? e->outt : e->B; }
+// at 16000 / float32 with one channel the _pcm entries ARE the plain ones; with more they are split -> the plain entry -> join
+bool plain_entry(const Engine* e) { return plain_format(e) && e->chn.C == 1; }
+
+// The callers' side of an entry in the layout in force, on stream s (the handle's device is current, every refusal is behind us).  pcm_in /
+// pcm_out: the callers' buffers [rows / C][n * C] -- either may be null: the entry has no such side.  rows_path(in, out) is the 1-channel
+// entry on [rows][n].  With one channel it gets the callers' buffers and nothing else happens; with more, pcm_in is split into the
+// library's buffer before rows_path runs and its result joined into pcm_out behind it, so pcm_in == pcm_out stays allowed.  The two buffers
+// are sized here, at call time, for the largest call the format in force allows (a block of max_frames hops, a packet): they grow only
+// behind a change of format or packet length, and those have synchronised.
+template <typename F>
+int through_channels(Engine* e, const void* pcm_in, void* pcm_out, int n, hipStream_t s, F rows_path) {
+  ChannelState& ch = e->chn;
+  if (ch.C == 1) return rows_path(pcm_in, pcm_out);
+  const int rows = handle_rows(e), bytes = static_cast<int>(sample_bytes(e));
+  const size_t most = std::max(static_cast<size_t>(max_hops(e)) * hop_samples(e), static_cast<size_t>(e->pkt.P));
+  if (int rc = grow_pair(e, rows * most * bytes, &ch.split, &ch.join, &ch.cap)) return rc;
+  const int q = static_cast<int>(static_cast<size_t>(n) * bytes / 16);
+  if (pcm_in) {
+    if (int rc = enqueue_on(e, s)) return rc;
+    HIP_TRY(launch_channels(bytes, ch.C, false, {pcm_in, ch.split, rows / ch.C, q}, s));
+  }
+  if (int rc = rows_path(pcm_in ? ch.split : nullptr, pcm_out ? ch.join : nullptr)) return rc;
+  if (pcm_out) {
+    if (int rc = enqueue_on(e, s)) return rc;
+    HIP_TRY(launch_channels(bytes, ch.C, true, {ch.join, pcm_out, rows / ch.C, q}, s));
+  }
+  return NUTLS_OK;
+}
+
+// The rule on the host: what nutls_pcm_deinterleave / nutls_pcm_interleave do.  in [outer][inner] -> out [inner][outer], elements of `bytes` bytes.
+void transpose_bytes(const unsigned char* in, unsigned char* out, size_t outer, size_t inner, size_t bytes) {
+  for (size_t i = 0; i < outer; ++i)
+    for (size_t j = 0; j < inner; ++j) std::copy_n(in + (i * inner + j) * bytes, bytes, out + (j * outer + i) * bytes);
+}
+
+int channels_host(const char* who, int fmt, int channels, const void* in, void* out, size_t n, bool join) {
+  const size_t bytes = fmt == NUTLS_PCM_F32 ? 4 : fmt == NUTLS_PCM_S16 ? 2 : g711_format(fmt) ? 1 : 0;
+  if (!bytes) return fail(NUTLS_ERR_ARG, std::string(who) + ": sample format must be NUTLS_PCM_F32, NUTLS_PCM_S16, NUTLS_PCM_ULAW or NUTLS_PCM_ALAW");
+  if (channels != 2 && channels != 4) return fail(NUTLS_ERR_ARG, std::string(who) + ": channels must be 2 or 4, not " + std::to_string(channels));
+  if (!in || !out) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
+  const size_t c = static_cast<size_t>(channels);
+  transpose_bytes(static_cast<const unsigned char*>(in), static_cast<unsigned char*>(out), join ? c : n, join ? n : c, bytes);
+  return NUTLS_OK;
+}
+
+// what the entries of one half on its own do behind their refusals: the callers' side is `in` of a decode, `out` of an encode
 int half_entry(nutls_handle* h, PcmDir dir, const void* in, void* out, const unsigned char* active, int n_hops, void* stream, const int* counts = nullptr) {
-  if (int rc = pcm_ready(&h->eng)) return rc;
-  return half_launch(&h->eng, dir, in, out, active, n_hops, static_cast<hipStream_t>(stream), counts);
+  Engine* e = &h->eng;
+  if (int rc = pcm_ready(e)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = n_hops * hop_samples(e);
+  if (dir == PcmDir::kDecode)
+    return through_channels(e, in, nullptr, n, s, [&](const void* rows, void*) { return half_launch(e, dir, rows, out, active, n_hops, s, counts); });
+  return through_channels(e, nullptr, out, n, s, [&](const void*, void* rows) { return half_launch(e, dir, in, rows, active, n_hops, s, counts); });
 }
 
 // the _host entries' staging of the callers' samples
@@ -206,26 +262,46 @@ int hop_refusals(nutls_handle* h, const unsigned char* active, int dc_mode, cons
   return NUTLS_OK;
 }
 
-// decode -> nutls_enhance_hop(_active) on the library's float buffers -> encode (active: device mask or null)
-int hop_device(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+// One row per stream: decode -> nutls_enhance_hop(_active) on the library's float buffers -> encode (active: device mask or null).  At
+// 16000 / float32 (reached with more than one channel only: plain_entry) the rows are the plain entry's.
+int hop_rows(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
   Engine* e = &h->eng;
   if (int rc = pcm_ready(e)) return rc;
+  if (plain_format(e)) return nutls_enhance_hop_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = half_launch(e, PcmDir::kDecode, pcm_in, e->pcm.f_in, active, 1, s)) return rc;
   if (int rc = nutls_enhance_hop_active(h, e->pcm.f_in, e->pcm.f_out, active, dc_mode, stream)) return rc;
   return half_launch(e, PcmDir::kEncode, e->pcm.f_out, pcm_out, active, 1, s);
 }
 
+// ... in the callers' layout
+int hop_device(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  if (int rc = pcm_ready(e)) return rc;
+  return through_channels(e, pcm_in, pcm_out, hop_samples(e), static_cast<hipStream_t>(stream),
+                          [&](const void* in, void* out) { return hop_rows(h, in, out, active, dc_mode, stream); });
+}
+
 // decode -> nutls_enhance_block(_ragged) on the library's float buffers -> encode.  hops: the DEVICE counts of a ragged block, handed to all
 // three parts, or null.  With counts the decode writes zero hops behind them into the library's buffer, nutls_enhance_block_ragged reads none
 // of them and writes zeros there, the encode reads none of those.
-int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+// One row per utterance; at 16000 / float32 (reached with more than one channel only: plain_entry) the rows are the plain entry's.
+int block_rows(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
   Engine* e = &h->eng;
   if (int rc = pcm_ready(e)) return rc;
+  if (plain_format(e)) return nutls_enhance_block_ragged(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, hops, dc_mode, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = half_launch(e, PcmDir::kDecode, pcm_in, e->pcm.f_in, nullptr, n_hops, s, hops)) return rc;
   if (int rc = nutls_enhance_block_ragged(h, e->pcm.f_in, e->pcm.f_out, n_hops, hops, dc_mode, stream)) return rc;      // (null hops: nutls_enhance_block)
   return half_launch(e, PcmDir::kEncode, e->pcm.f_out, pcm_out, nullptr, n_hops, s, hops);
+}
+
+// ... in the callers' layout
+int block_device(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
+  Engine* e = &h->eng;
+  if (int rc = pcm_ready(e)) return rc;
+  return through_channels(e, pcm_in, pcm_out, n_hops * hop_samples(e), static_cast<hipStream_t>(stream),
+                          [&](const void* in, void* out) { return block_rows(h, in, out, n_hops, hops, dc_mode, stream); });
 }
 
 // What the _host entries share, on the library's stream (the entry has put it behind what earlier calls queued on the callers' streams):
@@ -363,7 +439,7 @@ int packet_refusals(nutls_handle* h, bool pointers_ok, const unsigned char* acti
 // One hop round on the library's hop buffers: the existing hop entry of the handle's format (ready: DEVICE mask or null)
 int packet_hop(nutls_handle* h, const void* in, void* out, const unsigned char* ready, int dc_mode, hipStream_t s) {
   if (plain_format(&h->eng)) return nutls_enhance_hop_active(h, static_cast<const float*>(in), static_cast<float*>(out), ready, dc_mode, s);
-  return hop_device(h, in, out, ready, dc_mode, s);
+  return hop_rows(h, in, out, ready, dc_mode, s);      // (the library's hop buffers: one row per stream whatever the callers' layout)
 }
 
 // One tick on stream s (the handle's device is current, every refusal is behind us).  active: the DEVICE mask the kernels read, or null;
@@ -409,6 +485,12 @@ int packet_tick(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsign
     HIP_TRY(launch_packet(r + 1 < rounds ? PacketBody::kTurn : PacketBody::kTurnPop, L, s));
   }
   return NUTLS_OK;
+}
+
+// ... with the packets in the callers' layout
+int packet_device(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, const unsigned char* seen, int dc_mode, hipStream_t s) {
+  return through_channels(&h->eng, pcm_in, pcm_out, h->eng.pkt.P, s,
+                          [&](const void* in, void* out) { return packet_tick(h, in, out, active, seen, dc_mode, s); });
 }
 
 }  // namespace
@@ -564,7 +646,7 @@ int nutls_pcm_delay_samples(nutls_handle* h) {
 // ---- streaming handles ----------------------------------------------------------------------------------------------------------------------
 int nutls_enhance_hop_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode, void* stream) {
   if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm")) return rc;
-  if (plain_format(&h->eng)) return nutls_enhance_hop(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode, stream);
+  if (plain_entry(&h->eng)) return nutls_enhance_hop(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode, stream);
   if (int rc = hop_refusals(h, nullptr, dc_mode, "nutls_enhance_hop_pcm")) return rc;
   return hop_device(h, pcm_in, pcm_out, nullptr, dc_mode, stream);
 }
@@ -572,14 +654,14 @@ int nutls_enhance_hop_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, in
 int nutls_enhance_hop_pcm_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
   if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_active")) return rc;
   if (!active) return nutls_enhance_hop_pcm(h, pcm_in, pcm_out, dc_mode, stream);
-  if (plain_format(&h->eng)) return nutls_enhance_hop_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode, stream);
+  if (plain_entry(&h->eng)) return nutls_enhance_hop_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode, stream);
   if (int rc = hop_refusals(h, active, dc_mode, "nutls_enhance_hop_pcm_active")) return rc;
   return hop_device(h, pcm_in, pcm_out, active, dc_mode, stream);
 }
 
 int nutls_enhance_hop_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int dc_mode) {
   if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_host")) return rc;
-  if (plain_format(&h->eng)) return nutls_enhance_hop_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode);
+  if (plain_entry(&h->eng)) return nutls_enhance_hop_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), dc_mode);
   if (int rc = hop_refusals(h, nullptr, dc_mode, "nutls_enhance_hop_pcm_host")) return rc;
   return hop_host(h, pcm_in, pcm_out, nullptr, dc_mode);
 }
@@ -587,7 +669,7 @@ int nutls_enhance_hop_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_ou
 int nutls_enhance_hop_pcm_host_active(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode) {
   if (int rc = hop_args(h, pcm_in && pcm_out, "nutls_enhance_hop_pcm_host_active")) return rc;
   if (!active) return nutls_enhance_hop_pcm_host(h, pcm_in, pcm_out, dc_mode);
-  if (plain_format(&h->eng))
+  if (plain_entry(&h->eng))
     return nutls_enhance_hop_host_active(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), active, dc_mode);
   if (int rc = hop_refusals(h, active, dc_mode, "nutls_enhance_hop_pcm_host_active")) return rc;
   return hop_host(h, pcm_in, pcm_out, active, dc_mode);
@@ -682,7 +764,7 @@ int nutls_pcm_packet_fill(nutls_handle* h, int* fill, int n) {
 int nutls_enhance_packet_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, const unsigned char* active, int dc_mode, void* stream) {
   if (int rc = packet_refusals(h, pcm_in && pcm_out, active, dc_mode, "nutls_enhance_packet_pcm")) return rc;
   HIP_TRY(hipSetDevice(h->eng.device));
-  return packet_tick(h, pcm_in, pcm_out, active, nullptr, dc_mode, static_cast<hipStream_t>(stream));
+  return packet_device(h, pcm_in, pcm_out, active, nullptr, dc_mode, static_cast<hipStream_t>(stream));
 }
 
 // the tick through the staging (active: HOST mask or null): the host sees the mask, so the mirror of the counters stays known
@@ -700,20 +782,48 @@ int nutls_enhance_packet_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm
     d_act = e->pcm.d_active;
   }
   return through_staging(e, k.raw_in, k.raw_out, pcm_in, pcm_out, static_cast<size_t>(e->B) * k.P,
-                         [&](const void* in, void* out) { return packet_tick(h, in, out, d_act, active, dc_mode, e->stream); });
+                         [&](const void* in, void* out) { return packet_device(h, in, out, d_act, active, dc_mode, e->stream); });
+}
+
+// ---- channels: the callers' frame layout (streaming and offline handles) ------------------------------------------------------------------------
+int nutls_set_pcm_channels(nutls_handle* h, int channels) {
+  const char* who = "nutls_set_pcm_channels";
+  if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null handle");
+  Engine* e = &h->eng;
+  if (channels != 1 && channels != 2 && channels != 4)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": channels must be 1 (off), 2 or 4, not " + std::to_string(channels));
+  if (handle_rows(e) % channels)
+    return fail(NUTLS_ERR_ARG, std::string(who) + ": the handle has " + std::to_string(handle_rows(e)) + (e->offline ? " utterances" : " streams") +
+                                   ", which is no multiple of " + std::to_string(channels) + " channels: every frame row holds one stream per channel");
+  if (channels == e->chn.C) return NUTLS_OK;      // nothing is touched
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());      // a setting like the attenuation limit: it holds from the next call, behind everything queued so far
+  e->chn.C = channels;
+  return NUTLS_OK;
+}
+
+int nutls_pcm_channels(nutls_handle* h) { return h ? h->eng.chn.C : fail(NUTLS_ERR_ARG, "nutls_pcm_channels: null handle"); }
+
+// host only: the library's statement of the rule (no handle, no device)
+int nutls_pcm_deinterleave(int sample_format, int channels, const void* frames, void* rows, size_t n) {
+  return channels_host("nutls_pcm_deinterleave", sample_format, channels, frames, rows, n, false);
+}
+
+int nutls_pcm_interleave(int sample_format, int channels, const void* rows, void* frames, size_t n) {
+  return channels_host("nutls_pcm_interleave", sample_format, channels, rows, frames, n, true);
 }
 
 // ---- offline handles --------------------------------------------------------------------------------------------------------------------------
 int nutls_enhance_block_pcm(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode, void* stream) {
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_pcm")) return rc;
-  if (plain_format(&h->eng)) return nutls_enhance_block(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode, stream);
+  if (plain_entry(&h->eng)) return nutls_enhance_block(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode, stream);
   if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm")) return rc;
   return block_device(h, pcm_in, pcm_out, n_hops, nullptr, dc_mode, stream);
 }
 
 int nutls_enhance_block_pcm_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, int dc_mode) {
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, "nutls_enhance_block_pcm_host")) return rc;
-  if (plain_format(&h->eng)) return nutls_enhance_block_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode);
+  if (plain_entry(&h->eng)) return nutls_enhance_block_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, dc_mode);
   if (int rc = dc_ok(dc_mode, "nutls_enhance_block_pcm_host")) return rc;
   Engine* e = &h->eng;
   if (int rc = pcm_ready(e)) return rc;
@@ -736,7 +846,7 @@ int nutls_pcm_encode_block(nutls_handle* h, const float* wave_in, void* pcm_out,
 int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream) {
   const char* who = "nutls_enhance_block_pcm_ragged";
   if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
-  if (plain_format(&h->eng))
+  if (plain_entry(&h->eng))
     return nutls_enhance_block_ragged(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, hops, dc_mode, stream);
   if (!hops) return nutls_enhance_block_pcm(h, pcm_in, pcm_out, n_hops, dc_mode, stream);
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;
@@ -749,7 +859,7 @@ int nutls_enhance_block_pcm_ragged(nutls_handle* h, const void* pcm_in, void* pc
 int nutls_enhance_block_pcm_ragged_host(nutls_handle* h, const void* pcm_in, void* pcm_out, int n_hops, const int* hops, int dc_mode) {
   const char* who = "nutls_enhance_block_pcm_ragged_host";
   if (!h) return fail(NUTLS_ERR_ARG, std::string(who) + ": null pointer");
-  if (plain_format(&h->eng))
+  if (plain_entry(&h->eng))
     return nutls_enhance_block_ragged_host(h, static_cast<const float*>(pcm_in), static_cast<float*>(pcm_out), n_hops, hops, dc_mode);
   if (!hops) return nutls_enhance_block_pcm_host(h, pcm_in, pcm_out, n_hops, dc_mode);
   if (int rc = block_args(h, pcm_in && pcm_out, n_hops, who)) return rc;

@@ -16,6 +16,7 @@
 #include "ragged.hpp"
 #include "pcm.hpp"
 #include "packet.hpp"
+#include "channels.hpp"
 
 namespace nutls {
 
@@ -205,6 +206,7 @@ struct Engine {
   // ---- PCM gateway ---------------------------------------------------------------------------
   PcmState pcm;          // the callers' sample rate and type (nutls_set_pcm_format) and the resampler histories of the _pcm entries
   PacketState pkt;       // packet mode (nutls_set_pcm_packet): the callers' packet length, the per-stream FIFOs and their counters
+  ChannelState chn;      // channels (nutls_set_pcm_channels): the callers' frame layout and the two buffers the split and the join work between
 
   ~Engine() {
     for (int i = 0; i < 2; ++i)

@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     "nutls_set_atten_limit", "nutls_atten_limit", "nutls_istft_block_mix",
     "nutls_pcm_packet_plan", "nutls_set_pcm_packet", "nutls_pcm_packet_samples", "nutls_pcm_packet_delay_samples", "nutls_pcm_packet_fill",
     "nutls_pcm_packet_last_rounds", "nutls_enhance_packet_pcm", "nutls_enhance_packet_pcm_host",
+    "nutls_set_pcm_channels", "nutls_pcm_channels", "nutls_pcm_deinterleave", "nutls_pcm_interleave",
 )
 # ... and the declared symbols whose names carry a digit, listed apart: tests/test_abi.py compares ABI_SYMBOLS with the names it finds in
 # the header by a pattern of lower-case letters and underscores, which cannot see these
@@ -189,6 +190,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.nutls_pcm_packet_last_rounds.argtypes = [vp]
         lib.nutls_enhance_packet_pcm.argtypes = [vp, vp, vp, vp, c.c_int, vp]
         lib.nutls_enhance_packet_pcm_host.argtypes = [vp, vp, vp, vp, c.c_int]
+    if not dev_lib or hasattr(lib, "nutls_set_pcm_channels"):
+        lib.nutls_set_pcm_channels.argtypes = [c.c_void_p, c.c_int]
+        lib.nutls_pcm_channels.argtypes = [c.c_void_p]
+        lib.nutls_pcm_deinterleave.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_size_t]
+        lib.nutls_pcm_interleave.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_size_t]
     if not dev_lib or hasattr(lib, "nutls_pcm_g711_expand"):
         lib.nutls_pcm_g711_expand.argtypes = [c.c_int, c.POINTER(c.c_short), c.c_int]
         lib.nutls_pcm_g711_compress.argtypes = [c.c_int, c.POINTER(c.c_short), c.POINTER(c.c_ubyte), c.c_size_t]
@@ -316,6 +322,33 @@ def g711_compress(codec: str, samples, lib: Optional[ctypes.CDLL] = None) -> np.
     return out
 
 
+# Channels (nutls_set_pcm_channels): the sample types of the two host functions and their format codes (one byte is one byte: either law)
+_CHANNEL_FORMATS = {"float32": 0, "int16": 1, "uint8": 2}
+
+
+def _channel_layout(fn_name: str, x, frames_in: bool, lib) -> np.ndarray:
+    x = np.asarray(x)
+    if x.dtype.name not in _CHANNEL_FORMATS or x.ndim != 2:
+        raise ValueError("%s takes a 2-D float32, int16 or uint8 array, got %s %s" % (fn_name, x.dtype.name, x.shape))
+    x = np.ascontiguousarray(x)
+    n, ch = x.shape if frames_in else x.shape[::-1]
+    lib = lib or load_library()
+    out = np.empty((ch, n) if frames_in else (n, ch), x.dtype)
+    _check(lib, getattr(lib, fn_name)(_CHANNEL_FORMATS[x.dtype.name], int(ch), x.ctypes.data, out.ctypes.data, int(n)))
+    return out
+
+
+def pcm_deinterleave(frames, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
+    """Frames ``[n, C]`` (the layout of ``scipy.io.wavfile`` / ``soundfile``; float32, int16 or uint8, C 2 or 4) -> one row per channel,
+    ``[C, n]``: the rule of ``set_pcm_channels``, stated by the library (``nutls_pcm_deinterleave``).  Host only: needs no GPU."""
+    return _channel_layout("nutls_pcm_deinterleave", frames, True, lib)
+
+
+def pcm_interleave(rows, lib: Optional[ctypes.CDLL] = None) -> np.ndarray:
+    """One row per channel ``[C, n]`` -> frames ``[n, C]``: the inverse of :func:`pcm_deinterleave` (``nutls_pcm_interleave``)."""
+    return _channel_layout("nutls_pcm_interleave", rows, False, lib)
+
+
 def atten_limit_from_db(db) -> np.float32:
     """The attenuation limit ``l`` of a cap of ``db`` decibels on the noise removed: ``float32(10 ** (-db / 20))``; 0 dB -> 1 (nothing is
     removed), ``None`` -> 0 (no cap: the model's full suppression).  ``ValueError``: a negative or NaN value."""
@@ -435,18 +468,56 @@ class _PcmFormat:
         comes on top."""
         return int(self._lib.nutls_pcm_delay_samples(self._h))
 
+    def set_pcm_channels(self, channels: int = 1) -> None:
+        """The callers' frame layout of the ``_pcm`` methods (``nutls_set_pcm_channels``): 1, the default, is one row per stream; with 2
+        or 4 the callers' buffers are interleaved frames, ``[rows / C, n * C]`` or, the same memory, ``[rows / C, n, C]`` -- channel ``c`` of
+        frame row ``r`` is stream ``r * C + c`` -- and the methods return the shape they were given.  Masks, hop counts, limits and the
+        16 kHz float sides of the halves stay per stream.  A setting, not stream state: ``reset`` and ``set_pcm_format`` keep it, it may
+        change between any two calls and touches no history.  Synchronises the device.  ``ValueError``: a value other than 1, 2, 4, or one
+        that does not divide the handle's rows -- nothing changes."""
+        if int(channels) == self._pcm_channels:
+            return      # (the value in force: a no-op in the library too)
+        _check(self._lib, self._lib.nutls_set_pcm_channels(self._h, int(channels)))
+        self._pcm_channels = int(channels)
+
+    @property
+    def pcm_channels(self) -> int:
+        """Channels per frame of the callers' buffers (``nutls_pcm_channels``); 1: one row per stream."""
+        return int(self._lib.nutls_pcm_channels(self._h)) if self._pcm_channels > 1 else 1
+
+    _pcm_channels = 1      # what set_pcm_channels last set: the methods' shape checks cost no call into the library
+
+    def _pcm_shapes(self, rows: int, cols: int):
+        """The shapes the callers' side ``[rows, cols]`` of a ``_pcm`` method may have in the layout in force (the first: what the methods allocate)."""
+        ch = self._pcm_channels
+        return ((rows, cols),) if ch == 1 else ((rows // ch, cols * ch), (rows // ch, cols, ch))
+
+    def _pcm_cols(self, x) -> int:
+        """Samples per stream of the callers' buffer ``x`` in the layout in force; -1: not a shape of that layout."""
+        shape, ch = tuple(getattr(x, "shape", ())), self._pcm_channels
+        if ch > 1 and len(shape) == 3 and shape[2] == ch:
+            return int(shape[1])
+        return int(shape[1]) // ch if len(shape) == 2 and shape[1] % ch == 0 else -1
+
     def _pcm_tensor(self, x, rows: int, cols: int, name: str, dtype=None):
-        """A contiguous CUDA tensor ``[rows, cols]`` of the handle's sample type (or ``dtype``)."""
+        """A contiguous CUDA tensor ``[rows, cols]`` of the handle's sample type (or ``dtype``: a 16 kHz float side, one row per stream
+        whatever the layout); with channels, ``[rows / C, cols * C]`` or ``[rows / C, cols, C]``."""
         import torch
         want = dtype or getattr(torch, self.pcm_dtype)
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == want and x.is_contiguous() and tuple(x.shape) == (rows, cols)):
-            raise ValueError("%s must be a contiguous %s CUDA tensor [%d,%d]" % (name, str(want).replace("torch.", ""), rows, cols))
+        shapes = ((rows, cols),) if dtype is not None else self._pcm_shapes(rows, cols)
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == want and x.is_contiguous() and tuple(x.shape) in shapes):
+            raise ValueError("%s must be a contiguous %s CUDA tensor %s" % (name, str(want).replace("torch.", ""), self._shapes_text(shapes)))
         return x
 
     def _pcm_array(self, x, rows: int, cols: int, name: str):
-        if not (isinstance(x, np.ndarray) and x.dtype.name == self.pcm_dtype and x.flags.c_contiguous and x.shape == (rows, cols)):
-            raise ValueError("%s must be a contiguous %s numpy array [%d,%d]" % (name, self.pcm_dtype, rows, cols))
+        shapes = self._pcm_shapes(rows, cols)
+        if not (isinstance(x, np.ndarray) and x.dtype.name == self.pcm_dtype and x.flags.c_contiguous and x.shape in shapes):
+            raise ValueError("%s must be a contiguous %s numpy array %s" % (name, self.pcm_dtype, self._shapes_text(shapes)))
         return x
+
+    @staticmethod
+    def _shapes_text(shapes) -> str:
+        return " or ".join("[%s]" % ",".join("%d" % d for d in s) for s in shapes)
 
 
 # the kinds of the per-layer conv kernels, in the library's order (csrc/nutls_internal.hpp ConvKind)
@@ -738,7 +809,7 @@ class NutlsEngine(_PcmFormat):
         import torch
         x = self._pcm_tensor(hop, self.batch, 256, "hop", torch.float32)
         S = self.pcm_hop_samples
-        o = torch.empty((self.batch, S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None else self._pcm_tensor(out, self.batch, S, "out")
+        o = torch.empty(self._pcm_shapes(self.batch, S)[0], dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None else self._pcm_tensor(out, self.batch, S, "out")
         a = None if active is None else self._device_mask(active, x)
         _check(self._lib, self._lib.nutls_pcm_encode_hop(self._h, x.data_ptr(), o.data_ptr(), a, torch.cuda.current_stream(x.device).cuda_stream))
         return o
@@ -1277,7 +1348,7 @@ class NutlsOffline(_PcmFormat):
         import torch
         dc = self._dc(dc_mode)
         S = self.pcm_hop_samples
-        n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
+        n = self._pcm_block_hops(self._pcm_cols(pcm), S, "pcm")
         x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
         o = torch.empty_like(x) if out is None else self._pcm_tensor(out, self.utterances, n * S, "out")
         stream = torch.cuda.current_stream(x.device).cuda_stream
@@ -1291,7 +1362,7 @@ class NutlsOffline(_PcmFormat):
         """The same on host arrays (``nutls_enhance_block_pcm_host``; synchronous)."""
         dc = self._dc(dc_mode)
         S = self.pcm_hop_samples
-        n = self._pcm_block_hops(pcm.shape[-1] if isinstance(pcm, np.ndarray) and pcm.ndim == 2 else -1, S, "pcm")
+        n = self._pcm_block_hops(self._pcm_cols(pcm) if isinstance(pcm, np.ndarray) else -1, S, "pcm")
         x = self._pcm_array(pcm, self.utterances, n * S, "pcm")
         o = np.empty_like(x) if out is None else self._pcm_array(out, self.utterances, n * S, "out")
         _check(self._lib, self._lib.nutls_enhance_block_pcm_host(self._h, x.ctypes.data, o.ctypes.data, n, dc))
@@ -1302,7 +1373,7 @@ class NutlsOffline(_PcmFormat):
         float32 at 16 kHz (what ``enhance_block_device`` takes).  ``hops``: per-utterance counts (``nutls_pcm_decode_block_ragged``)."""
         import torch
         S = self.pcm_hop_samples
-        n = self._pcm_block_hops(int(pcm.shape[-1]) if hasattr(pcm, "shape") and len(pcm.shape) == 2 else -1, S, "pcm")
+        n = self._pcm_block_hops(self._pcm_cols(pcm), S, "pcm")
         x = self._pcm_tensor(pcm, self.utterances, n * S, "pcm")
         o = (torch.empty((self.utterances, n * 256), dtype=torch.float32, device=x.device) if out is None
              else self._pcm_tensor(out, self.utterances, n * 256, "out", torch.float32))
@@ -1320,7 +1391,7 @@ class NutlsOffline(_PcmFormat):
         S = self.pcm_hop_samples
         n = self._pcm_block_hops(int(wave.shape[-1]) if hasattr(wave, "shape") and len(wave.shape) == 2 else -1, 256, "wave")
         x = self._pcm_tensor(wave, self.utterances, n * 256, "wave", torch.float32)
-        o = (torch.empty((self.utterances, n * S), dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None
+        o = (torch.empty(self._pcm_shapes(self.utterances, n * S)[0], dtype=getattr(torch, self.pcm_dtype), device=x.device) if out is None
              else self._pcm_tensor(out, self.utterances, n * S, "out"))
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if hops is None:
@@ -1330,13 +1401,13 @@ class NutlsOffline(_PcmFormat):
         return o
 
     def _wave_through_blocks(self, x: np.ndarray, lag: int, block) -> np.ndarray:
-        """``x [utterances, N]`` of the handle's sample type, padded with zeros (G.711: the silence code) to whole hops that cover ``N + lag`` samples, through
+        """``x [utterances, N]`` (with channels: ``[utterances / C, N, C]``) of the handle's sample type, padded with zeros (G.711: the silence code) to whole hops that cover ``N + lag`` samples, through
         ``block`` (array ``[utterances, n_hops * pcm_hop_samples]`` -> array of the same shape, n_hops <= max_frames) in blocks of
         ``max_frames`` hops; the first ``lag`` samples of the result are dropped, so that sample i of what is returned belongs to ``x[:, i]``."""
         S = self.pcm_hop_samples
         n = x.shape[1]
         hops = max(1, -(-(n + lag) // S))
-        padded = np.full((self.utterances, hops * S), self.pcm_silence, x.dtype)
+        padded = np.full((x.shape[0], hops * S) + x.shape[2:], self.pcm_silence, x.dtype)
         padded[:, :n] = x
         out = np.empty_like(padded)
         for a in range(0, hops, self.max_frames):
@@ -1373,10 +1444,12 @@ class NutlsOffline(_PcmFormat):
         rate); the padding is then the law's silence code, the result uint8 codes of the same law.  ``upper_gain``: the gain of the band
         above 8 kHz of a 32 or 48 kHz recording, passed around the model (``set_pcm_upper_band``, set after the format); 0.0: the result is
         band-limited to 8 kHz.  ``upper_follow``: that gain is the ceiling of one that follows the model's suppression
-        (``set_pcm_upper_follow``, set after the gain)."""
+        (``set_pcm_upper_follow``, set after the gain).  One row per utterance: the handle's layout becomes 1 channel
+        (``set_pcm_channels``); interleaved frames ``[N, C]``: :meth:`enhance_wave_channels`."""
         self._dc(dc_mode)
         x = np.asarray(wave)
         fmt = self._wave_format(x.dtype, rate, codec)
+        self.set_pcm_channels(1)
         batched = x.ndim == 2
         if x.ndim == 1 and self.utterances == 1:
             x = x[None]
@@ -1389,15 +1462,44 @@ class NutlsOffline(_PcmFormat):
         out = self._wave_through_blocks(x, lag, lambda blk: self.enhance_block_pcm_host(blk, None, dc_mode))
         return out if batched else out[0]
 
+    def enhance_wave_channels(self, wave, rate: int, channels: int, dc_mode: str = "edge", codec: Optional[str] = None, upper_gain: float = 0.0,
+                              upper_follow: bool = False) -> np.ndarray:
+        """:meth:`enhance_wave` of interleaved frames: ``wave [N, C]``, the layout of ``scipy.io.wavfile`` / ``soundfile``, on a handle of
+        ``utterances == C``, or ``[utterances / C, N, C]``, ``channels`` = C, 2 or 4.  Every channel is an utterance of its own
+        (``set_pcm_channels``, which stays in force): channel c of recording r is utterance ``r * C + c``, and the result -- same shape and
+        dtype, aligned like :meth:`enhance_wave`'s -- is bit for bit what :meth:`enhance_wave` returns for the transposed array on a
+        1-channel handle of the same shape.  The split and the join happen on the device.  (A method of its own, like
+        ``enhance_many_atten``: ``enhance_wave`` keeps the signature it has.)"""
+        self._dc(dc_mode)
+        x = np.asarray(wave)
+        fmt = self._wave_format(x.dtype, rate, codec)
+        if channels not in (2, 4):
+            raise ValueError("channels must be 2 or 4, got %r (one row per utterance: enhance_wave)" % (channels,))
+        self.set_pcm_channels(channels)      # (ValueError: the handle's utterances are no multiple of it)
+        batched = x.ndim == 3
+        if x.ndim == 2 and self.utterances == channels:
+            x = x[None]
+        if x.ndim != 3 or x.shape[0] * channels != self.utterances or x.shape[2] != channels:
+            raise ValueError("with channels=%d wave must be [%sN,%d], got %s" % (
+                channels, "%d," % (self.utterances // channels) if self.utterances > channels else "", channels, np.shape(x)))
+        self.set_pcm_format(rate, fmt)
+        self.set_pcm_upper_band(upper_gain)
+        self.set_pcm_upper_follow(upper_follow)
+        lag = self.pcm_hop_samples + self.pcm_delay_samples
+        out = self._wave_through_blocks(x, lag, lambda blk: self.enhance_block_pcm_host(blk, None, dc_mode))
+        return out if batched else out[0]
+
     # -- ragged blocks: per-utterance counts (nutls_process_block_ragged_host / nutls_enhance_block_ragged_host) ---------------------
-    def _ragged_host(self, entry, chunks, unit: int, *tail, dtype=None):
+    def _ragged_host(self, entry, chunks, unit: int, *tail, dtype=None, channels: int = 1):
         """One ragged block through a ``_host`` entry.  ``chunks[u]``: utterance u's piece of the block, ``k_u`` frames ``[k_u,256]``
         (``unit`` 1) or ``k_u`` hops of PCM ``[k_u * unit]`` (``unit`` 256: float32 at 16 kHz), k_u <= max_frames and at least one > 0; the
         row stride of the block is the longest count.  ``dtype``: the sample type of an entry that takes the callers' format (``unit`` =
-        ``pcm_hop_samples``, buffers handed over as addresses); None: float32.  Returns each utterance's piece of the result."""
+        ``pcm_hop_samples``, buffers handed over as addresses); None: float32.  Returns each utterance's piece of the result.
+        ``channels`` (``set_pcm_channels``): ``chunks[r]`` is frame row r's piece ``[k_r * unit, C]``, and each of its C utterances gets its count."""
         counts = np.array([c.shape[0] // unit for c in chunks], np.int32)
         n = int(counts.max())
-        blk = np.zeros((self.utterances, n * unit) + chunks[0].shape[1:], dtype or np.float32)
+        counts = np.ascontiguousarray(np.repeat(counts, channels))
+        blk = np.zeros((len(chunks), n * unit) + chunks[0].shape[1:], dtype or np.float32)
         for u, c in enumerate(chunks):
             blk[u, :c.shape[0]] = c
         out = np.empty_like(blk)
@@ -1451,8 +1553,34 @@ class NutlsOffline(_PcmFormat):
         dtype; each result then has its input's length and dtype and is ALIGNED with it, what :meth:`enhance_wave` of a fresh one-utterance
         handle returns (``nutls_enhance_block_pcm_ragged_host``).  Sets the handle's format, which turns the upper band
         (``set_pcm_upper_band``) and with it its following gain (``set_pcm_upper_follow``) off: the results are band-limited to 8 kHz.
-        uint8 arrays of G.711 codes are refused here (a dtype cannot say which law): :meth:`enhance_many_codec`."""
+        uint8 arrays of G.711 codes are refused here (a dtype cannot say which law): :meth:`enhance_many_codec`.  Recordings of
+        interleaved frames ``[N_i, C]``: :meth:`enhance_many_channels`."""
         return self._enhance_many(waves, dc_mode, rate, None)
+
+    def enhance_many_channels(self, waves, rate: int, channels: int, dc_mode: str = "edge", codec: Optional[str] = None,
+                              atten_lim_db=None) -> List[np.ndarray]:
+        """:meth:`enhance_many` for recordings of interleaved frames: each ``waves[i]`` is ``[N_i, C]``, ``channels`` = C, 2 or 4, at
+        ``rate`` (int16 or float32; uint8 G.711 codes with ``codec``, as in :meth:`enhance_many_codec`).  The scheduler plans
+        ``utterances // C`` frame rows (:func:`plan_ragged_blocks`); every channel of a row is an utterance of its own and gets the row's
+        hop count, its reset and the recording's limit (``atten_lim_db``: as in :meth:`enhance_many_atten`).  Each result has its input's
+        shape and dtype, aligned with it; ``set_pcm_channels`` stays in force.  The split and the join happen on the device
+        (``nutls_enhance_block_pcm_ragged_host``).  (A method of its own, like ``enhance_many_atten``: ``enhance_many`` keeps the
+        signature it has.)"""
+        dc = self._dc(dc_mode)
+        if channels not in (2, 4):
+            raise ValueError("channels must be 2 or 4, got %r (one row per utterance: enhance_many)" % (channels,))
+        waves = [np.asarray(w) for w in waves]
+        if codec is not None:
+            for w in waves:
+                self._wave_format(w.dtype, rate, codec)
+            self._wave_format(np.uint8, rate, codec)
+        limits = None
+        if atten_lim_db is not None:
+            seq = list(atten_lim_db) if isinstance(atten_lim_db, (list, tuple, np.ndarray)) else [atten_lim_db] * len(waves)
+            if len(seq) != len(waves):
+                raise ValueError("atten_lim_db must be a scalar or one value per recording (%d), got %d" % (len(waves), len(seq)))
+            limits = [atten_limit_from_db(d) for d in seq]
+        return self._enhance_many_pcm(waves, dc, rate, limits, codec, channels)
 
     def enhance_many_atten(self, waves, atten_lim_db, dc_mode: str = "edge", rate: Optional[int] = None) -> List[np.ndarray]:
         """:meth:`enhance_many` with an attenuation limit per recording: ``atten_lim_db`` a cap in dB on the noise removed, a scalar for
@@ -1472,7 +1600,8 @@ class NutlsOffline(_PcmFormat):
         other than uint8.  Each result is uint8 codes of the same law, has its input's length and is ALIGNED with it: what
         ``enhance_wave(w, 8000, codec=codec)`` of a fresh one-utterance handle returns.  Recordings are padded with the law's silence code.
         ``atten_lim_db``: as in :meth:`enhance_many_atten`, None for no cap on any recording.  (A method of its own, like
-        ``enhance_many_atten``: ``enhance_many`` keeps the signature it has, and refuses uint8 arrays.)"""
+        ``enhance_many_atten``: ``enhance_many`` keeps the signature it has, and refuses uint8 arrays.)  A stereo archive, ``[N_i, 2]``
+        arrays: :meth:`enhance_many_channels` with ``codec``."""
         dc = self._dc(dc_mode)
         waves = [np.asarray(w) for w in waves]
         for w in waves:
@@ -1486,14 +1615,15 @@ class NutlsOffline(_PcmFormat):
             limits = [atten_limit_from_db(d) for d in seq]
         return self._enhance_many_pcm(waves, dc, int(rate), limits, codec)
 
-    def _slot_limits(self, block, limits):
-        """The scheduler's hand-over of :meth:`enhance_many_atten`: the slots of ``block`` that take a new recording get its limit."""
+    def _slot_limits(self, block, limits, channels: int = 1):
+        """The scheduler's hand-over of :meth:`enhance_many_atten`: the slots of ``block`` that take a new recording get its limit (with
+        channels: every utterance of the slot's frame row)."""
         new = [] if limits is None else [(slot, limits[item]) for slot, item, _, _, reset_before in block if reset_before]
         if not new:
             return
         cur = self.atten_limit
         for slot, l in new:
-            cur[slot] = l
+            cur[slot * channels:(slot + 1) * channels] = l
         self.set_atten_limit(limit=cur)
 
     def _enhance_many(self, waves, dc_mode, rate, limits) -> List[np.ndarray]:
@@ -1520,13 +1650,16 @@ class NutlsOffline(_PcmFormat):
 
     _PCM_RATES = (8000, 16000, 32000, 48000)
 
-    def _enhance_many_pcm(self, waves, dc: int, rate, limits=None, codec=None) -> List[np.ndarray]:
+    def _enhance_many_pcm(self, waves, dc: int, rate, limits=None, codec=None, channels: int = 1) -> List[np.ndarray]:
         """:meth:`enhance_many` in the callers' format.  Every recording is padded with zeros to whole hops that cover ``N + lag`` samples,
         ``lag = pcm_hop_samples + pcm_delay_samples`` (the rule of :meth:`_wave_through_blocks`), and the lag is dropped from the front.
         ``codec`` (:meth:`enhance_many_codec`, which has checked dtype and rate): uint8 codes of that G.711 law, padded with its silence code."""
         waves = [np.asarray(w) for w in waves]
-        if any(w.ndim != 1 for w in waves):
-            raise ValueError("waves must be one-dimensional arrays")
+        if channels == 1:
+            if any(w.ndim != 1 for w in waves):
+                raise ValueError("waves must be one-dimensional arrays")
+        elif any(w.ndim != 2 or w.shape[1] != channels for w in waves):
+            raise ValueError("with channels=%r waves must be arrays [N,%r] of interleaved frames" % (channels, channels))
         names = {w.dtype.name for w in waves}
         if codec is None and (len(names) > 1 or not names <= {"float32", "int16"}):
             raise ValueError("with a rate, waves must all be int16 or all be float32 (uint8 G.711 codes: enhance_many_codec), got %s" % sorted(names))
@@ -1535,25 +1668,28 @@ class NutlsOffline(_PcmFormat):
         if not waves:
             return []
         dtype = waves[0].dtype
+        self.set_pcm_channels(channels)      # (ValueError: not 1, 2 or 4, or the handle's utterances are no multiple of it)
         self.set_pcm_format(int(rate), codec or dtype)
         S = self.pcm_hop_samples
         lag = S + self.pcm_delay_samples
         hops = [max(1, -(-(len(w) + lag) // S)) for w in waves]
         padded = []
         for w, n in zip(waves, hops):
-            p = np.full(n * S, self.pcm_silence, dtype)
+            p = np.full((n * S,) + w.shape[1:], self.pcm_silence, dtype)
             p[:len(w)] = w
             padded.append(p)
         outs = [np.empty_like(p) for p in padded]
-        empty = np.zeros(0, dtype)
-        for block in plan_ragged_blocks(hops, self.utterances, self.max_frames):
-            chunks = [empty] * self.utterances
+        empty = np.zeros((0,) + waves[0].shape[1:], dtype)
+        rows = self.utterances // channels      # frame rows: the scheduler's slots
+        for block in plan_ragged_blocks(hops, rows, self.max_frames):
+            chunks = [empty] * rows
             for slot, item, first, count, reset_before in block:
                 if reset_before:
-                    self.reset_utterance(slot)
+                    for u in range(slot * channels, (slot + 1) * channels):
+                        self.reset_utterance(u)
                 chunks[slot] = padded[item][first * S:(first + count) * S]
-            self._slot_limits(block, limits)
-            got = self._ragged_host(self._lib.nutls_enhance_block_pcm_ragged_host, chunks, S, dc, dtype=dtype)
+            self._slot_limits(block, limits, channels)
+            got = self._ragged_host(self._lib.nutls_enhance_block_pcm_ragged_host, chunks, S, dc, dtype=dtype, channels=channels)
             for slot, item, first, count, _ in block:
                 outs[item][first * S:(first + count) * S] = got[slot]
         return [o[lag:lag + len(w)] for o, w in zip(outs, waves)]
