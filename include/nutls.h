@@ -618,6 +618,53 @@ int nutls_atten_limit(nutls_handle* h, float* limit, int n);
  * Otherwise nutls_istft_block[_ragged]; with every limit 0 it launches their kernels and never reads noisy. */
 int nutls_istft_block_mix(nutls_handle* h, const float* est, const float* noisy, float* pcm_out, int n_hops, const int* hops, int dc_mode, void* stream);
 
+/* ---- Non-finite input: what a live row that goes bad may do to the others, and how it heals ---------------------------------------
+ * One handle serves many callers.  A workgroup steps two or four streams side by side, a per-layer tile of 128 positions spans several
+ * streams, in block mode a tile spans several frames and utterances, one stereo frame row carries two talkers, the corpus scheduler hands a
+ * slot to the next recording.  A row is a stream of a streaming handle or an utterance of an offline one.  "Poison" is anything a LIVE
+ * row is fed that is not a finite number that stays finite: NaN, +-Inf, or finite values that overflow inside (a magnitude row of 3e38).
+ * (A HELD row and the rows behind a ragged count may hold anything because they have no effect; that is said where those are defined.)
+ *   1. Containment across rows.  Whatever one row is fed, EVERY OTHER ROW of the handle is bit-identical to the run in which that row was
+ *      fed zeros instead: outputs, all state tensors of nutls_state_get, and every per-row library state (previous hop, overlap tail,
+ *      resampler histories, upper band, nutls_pcm_follow_gain, nutls_pcm_packet_fill, the causal32 attention history).  On every entry,
+ *      plan (1, 2, 4 streams per workgroup), mode (0, 1, 3), variant, CTFA mode, with nutls_debug_trace on or off, hop fusion on or off, in
+ *      the callers' formats, with channels and packets.  No row is ever combined with another under a weight or a mask of zero: 0 x NaN
+ *      is NaN, so "excluded" means not read, or selected away, never multiplied away.
+ *   2. Containment in time (block entries).  Every layer is causal in time: poison in frame t of an utterance leaves that utterance's
+ *      output rows 0 .. t-1 of the call (and everything earlier calls returned) bit-identical to the clean run.  Waveform entries: input
+ *      hop t makes frames t and t + 1, and output hop t is the first half of synthesis block t plus the second half of block t - 1; so
+ *      poison in input hop t leaves output hops 0 .. t-1 -- samples 0 .. 256 t - 1 of the utterance -- bit-identical, and output hop t, which
+ *      carries the signal of input hop t - 1 (the one-hop lag), is the first that may differ.  In the callers' format the same holds with
+ *      the decode half's window below in front: caller's sample n reaches 16 kHz sample ceil(n / q) at the earliest.
+ *   3. Finite support of the stateless halves.  The transforms, the resamplers, the upper band and follow have no recurrence: through
+ *      nutls_stft_hop / nutls_istft_hop, nutls_stft_block / nutls_istft_block, nutls_pcm_decode_* / nutls_pcm_encode_* ALONE one poisoned
+ *      input sample may change only the outputs inside the windows below; every output outside is bit-identical to the clean run, and the
+ *      row is finite again behind the window.  T = nutls_pcm_filter_taps(rate), L = T - 1, q = max(rate, 16000) / min(rate, 16000),
+ *      S = nutls_pcm_hop_samples, W = NUTLS_PCM_FOLLOW_HOPS; L = nutls_pcm_delay_samples above 16 kHz and twice that at 8 kHz; all windows
+ *      closed, samples counted along the row's concatenated hops since its last reset:
+ *        rate reduction by q (decode above 16 kHz, encode at 8 kHz)   sample n -> samples ceil(n / q) .. floor((n + L) / q)
+ *        rate increase by q (decode at 8 kHz, encode above 16 kHz)    sample m -> samples q m .. q m + L
+ *        decode then encode (the model the identity, no lag)          sample n -> samples n' .. n'' + 2 nutls_pcm_delay_samples, with n', n''
+ *                                                                     = n rounded up, down to a multiple of q above 16 kHz, = n at 8 kHz
+ *        analysis (nutls_stft_hop, nutls_stft_block)                  sample n -> magnitude and phasor frames floor(n / 256) and the next
+ *        synthesis (nutls_istft_hop, nutls_istft_block)               frame f, a magnitude or a phasor -> samples 256 f .. 256 (f + 2) - 1
+ *        analysis then synthesis (frame 512, hop 256)                 sample n -> the three output hops floor(n / 256) .. floor(n / 256) + 2
+ *        upper band, u recorded by the decode half                    sample n -> u[n' .. n'' + 2 L], added by the encode half S samples
+ *                                                                     later: output samples n' + S .. n'' + 2 L + S
+ *        follow, energy a_s of decoded hop s not finite                -> the whole output hops s + 1 .. s + W + 1 (A_t sums a_(t-1) .. a_(t-W),
+ *                                                                     and gamma_t ramps from g_(t-1) to g_t)
+ *        follow, energy b_s of an encoded hop s not finite             -> the whole output hops s .. s + W
+ *      (fminf / fmaxf return their finite argument, so a NaN energy may give a finite gain: still inside the window.)
+ *   4. Healing.  After nutls_reset(h, b) row b is bit-identical to the same row of a FRESH handle of the same configuration fed the same
+ *      continuation, whatever the row held -- NaN and Inf included: everything a reset restarts is rewritten (memset: zeros, or the silence
+ *      that primes a packet FIFO), never scaled by zero.  The same holds for the histories that nutls_set_pcm_format, nutls_set_pcm_upper_band, nutls_set_pcm_upper_follow,
+ *      nutls_set_pcm_packet and a CTFA mode switch restart.  Rows that are not reset are untouched.  Without a reset a poisoned row stays
+ *      poisoned for as long as its recurrent state is (NaN in an LSTM cell never decays).
+ *   5. Not specified: what the poisoned row itself returns, beyond the rules above and those that already exist (NaN -> 0 -> the silence
+ *      code on the int16 / G.711 encode).
+ * tests/poison_reference.py states the windows, tests/test_poison_reference.py holds them against float64, tests/test_gpu_poison.py holds
+ * the kernels to 1 - 4, bit for bit. */
+
 /* Library-owned device staging buffers [B,256]; stepping on them avoids the D2D copies and lets
  * the captured hipGraph run with no per-call parameter update. */
 int nutls_io_buffers(nutls_handle* h, float** mag_in, float** mag_out);

@@ -13,7 +13,8 @@ sequence of calls runs on a fresh non-blocking side stream behind a GATE:
   4. the library calls of the sequence are made with no host synchronisation between them;
   5. the host synchronises only at the end.
 
-Whatever the library queued elsewhere runs during the sleep, on poison or on stale state; NaN in the model state never heals, so the
+Whatever the library queued elsewhere runs during the sleep, on poison or on stale state; NaN in the model state never heals until
+``nutls_reset`` (tests/test_gpu_poison.py holds that it does then, and that it never reaches another row), so the
 comparison with the synchronous run of the same sequence (``Seq(gated=False)``: default stream, a synchronisation after every call)
 sees it.  A gated run counts only if the marker is still incomplete when the last non-blocking call of the sequence has returned
 (``Seq.check_held``, called by ``Seq.close`` or by the test just before the first host-blocking call): otherwise the run fails with
